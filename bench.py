@@ -9,6 +9,11 @@ region.  One step = detect -> LM-fit every candidate -> R^2 filter + consolidati
 (+ the RCCL gather of the peak tables to rank 0 when N > 1).  The K timed steps are K batches streamed through
 engine.StreamPipeline (continuous batching of the LM fits; --pipeline lanes runs every step stand-alone).
 value = candidate LM solves per second, whole job.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only.  --full adds the side measurements to the same line: `extras` (single GPU: the
+H2D-inclusive pipeline, the pflib surface, the command line, registration, tracking, photometry, the fp32 solver) and
+`cpu_baseline` (the oracle on the host's cores).  --dump-outputs DIR writes what the last timed step computed as .npy files
+(see peak_outputs).
 """
 import argparse
 import json
@@ -82,8 +87,12 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 3),
                     help="2: BASELINE configs[1], detect + fit + consolidate (the headline); 3: the registration step of configs[2] "
                          "(phase correlation of consecutive cycle frames, upsample_factor 20) - pairs/s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the H2D-inclusive and dict-materialising side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements (extras, cpu_baseline) after the headline; a plain run takes none")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the H2D-inclusive and dict-materialising side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's fields) as DIR/<name>.npy")
     ap.add_argument("--materialise", action="store_true",
                     help="N > 1: every step's gathered peak RECORDS (378 B per peak, not just the 128 B rows) go to rank 0 and "
                          "rank 0 builds the reference's dicts from them inside the timed region (distributed.py's dict form)")
@@ -128,7 +137,9 @@ def main():
         res = run_stream(a, torch, dist, D, E, N, d_img, imgs, prm, dev, rank, world)
     else:
         res = run_lanes(a, torch, dist, D, E, N, d_img, prm, dev, rank, world)
-    dt, total, kept, busy_ms, fit_launches, how, cand_tables = res
+    dt, total, kept, busy_ms, fit_launches, how, cand_tables, outputs = res
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs())
 
     tt = torch.tensor([dt, float(total), float(kept)], dtype=torch.float64, device=dev)
     if world > 1:
@@ -189,9 +200,9 @@ def main():
                                  "traffic_GBps": (traffic * a.steps / (busy_ms * 1e-3) / 1e9) if traffic else None,
                                  "peak_GBps": PEAK_HBM_GBS}},
         }
-        if not a.no_extras and world == 1:
+        if a.full and not a.no_extras and world == 1:
             out["extras"] = extras(a, torch, E, N, pflib, imgs, d_img, prm, dev)
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             cand, counts, offsets = cand_tables()
             n_thr = min(16, len(os.sched_getaffinity(0)))     # the box's CPU share for one GPU
             out["cpu_baseline"] = cpu_baseline(imgs, cand, counts, offsets, n_thr)
@@ -248,6 +259,46 @@ def launch_ranks(a, argv=None, run=None):
     return 0
 
 
+DUMP_BYTES = 64 * 10**6         # --dump-outputs: at most this much in all
+
+
+def peak_outputs(engines, cut, N):
+    """The last timed step's results as its caller receives them, engine k holding the fields cut[k] .. cut[k+1]:
+    kept_rows    float64[k, 20]  the kept peak table (Engine.kept_table) in field order, one column per N.ROW_DTYPE field
+                                 (h0 .. p3, then h, w, field, status, niter, nfev, key_h, key_w; `field` counted over the batch)
+    kept_per_field, candidates_per_field   float64[n_fields]  (kept -1: the reference's re-key assert fired for that field)
+    kept_rows_fields   float64[m]  the fields whose rows kept_rows holds: all of them, or, when the whole table would not fit
+                                   DUMP_BYTES, as many as fit taken in a fixed seeded order (their rows complete)."""
+    names = N.ROW_DTYPE.names
+    fcol = names.index("field")
+    tabs, kept, cands = [], [], []
+    for k, eng in enumerate(engines):
+        rows = eng.kept_table()[0].cpu().numpy().view(N.ROW_DTYPE).reshape(-1)
+        t = np.stack([rows[c].astype(np.float64) for c in names], axis=1).reshape(-1, len(names))
+        t[:, fcol] += cut[k]
+        tabs.append(t)
+        kept.append(eng.nkeep[:eng.n_fields].cpu().numpy().astype(np.float64))
+        cands.append(eng.counts[:eng.n_fields].cpu().numpy().astype(np.float64))
+    rows, kept, cands = np.concatenate(tabs), np.concatenate(kept), np.concatenate(cands)
+    n = len(kept)
+    budget = DUMP_BYTES - 3 * n * 8
+    per_field = np.bincount(rows[:, fcol].astype(np.int64), minlength=n) * rows.shape[1] * 8
+    order = np.random.default_rng(0).permutation(n)
+    fields = np.sort(order[np.cumsum(per_field[order]) <= budget])
+    if len(fields) < n:
+        rows = rows[np.isin(rows[:, fcol].astype(np.int64), fields)]
+    return {"kept_rows": rows, "kept_rows_fields": fields.astype(np.float64), "kept_per_field": kept,
+            "candidates_per_field": cands}
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_BYTES
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 REG_BYTES_PER_PX = 2 * (2 + 8) + 2 * 4 * 8 + (16 + 16 + 8) + 4 * 8 + 8 + 2 * 8      # = 180
 # fp64 real-transform registration, per pixel of a pair: 2 images uint16 -> float64 (2 B in, 8 B out each); two forward
 # real-to-complex FFTs of two passes each (8 B in + 8 B out per pass: a half spectrum is 8 B per pixel); cross-power
@@ -284,7 +335,8 @@ def measure_registration(torch, E, N, size, spots, steps, warmup, rank=0, barrie
         barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return {"pairs": n, "seconds": dt, "launch_ms": ev0.elapsed_time(ev1) / steps, "bytes_per_call": REG_BYTES_PER_PX * H * W * n}
+    return {"pairs": n, "seconds": dt, "launch_ms": ev0.elapsed_time(ev1) / steps, "bytes_per_call": REG_BYTES_PER_PX * H * W * n,
+            "out": out}
 
 
 def bench_registration(a, torch, dist, D, E, N):
@@ -295,6 +347,8 @@ def bench_registration(a, torch, dist, D, E, N):
     H = W = a.size
     m = measure_registration(torch, E, N, a.size, a.spots, a.steps, a.warmup, rank, lambda: _barrier(torch, dist, world))
     n, dt = m["pairs"], m["seconds"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"registration": m["out"].cpu().numpy()})       # Registrar.register's float64[pairs, 4]
     tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -339,10 +393,14 @@ def run_stream(a, torch, dist, D, E, N, d_img, imgs, prm, dev, rank, world):
     kept = [0] * Q
     box = _queue.Queue()
     built = [0]
+    n_jobs = [0]
+    last = [None] * Q                               # the engine holding queue k's share of the latest run's last step
     from fluorosequencingimageanalysis_amd import pflib as pflib_mod
 
     def on_done(j, k, eng, total):
         kept[k] = eng.nkeep[eng.n_fields]           # (device scalar; read after the run)
+        if j == n_jobs[0] - 1:                      # (no later job of the run re-uses this engine)
+            last[k] = eng
         if world > 1:
             if a.materialise:                       # the full peak records (FsqRow + fit_img + sub_img) and the per-field counts
                 table = eng.peak_records(d_img[group.cut[k]:group.cut[k + 1]])[0]
@@ -355,6 +413,7 @@ def run_stream(a, torch, dist, D, E, N, d_img, imgs, prm, dev, rank, world):
 
     def steps(n):
         res, errs = [None], []
+        n_jobs[0] = n
 
         def body():
             try:
@@ -412,7 +471,8 @@ def run_stream(a, torch, dist, D, E, N, d_img, imgs, prm, dev, rank, world):
     def cand_tables():
         e = E.Engine(a.fields, a.size, a.size, device=dev, fit_workspace=False)
         return e.candidates(e.detect(d_img, prm))
-    return dt, totals[0], sum(int(x) for x in kept), busy_ms, {"rounds": rounds, "steps": a.steps, "queues": Q}, how, cand_tables
+    return (dt, totals[0], sum(int(x) for x in kept), busy_ms, {"rounds": rounds, "steps": a.steps, "queues": Q}, how, cand_tables,
+            lambda: peak_outputs(last, group.cut, N))
 
 
 def run_lanes(a, torch, dist, D, E, N, d_img, prm, dev, rank, world):
@@ -466,7 +526,7 @@ def run_lanes(a, torch, dist, D, E, N, d_img, prm, dev, rank, world):
     kept = sum(int(e.nkeep[e.n_fields]) for e in engs)
     how = "every step a stand-alone batch worked as %d share(s) on their own HIP streams" % lanes
     return (dt, total, kept, busy_ms, {"fit_calls": lanes * a.steps}, how,
-            lambda: engs[0].candidates(totals[0][0]))
+            lambda: engs[0].candidates(totals[0][0]), lambda: peak_outputs(engs, cut, N))
 
 
 def extras(a, torch, E, N, pflib, imgs, d_img, prm, dev):

@@ -221,6 +221,49 @@ def test_bench_with_mismatched_world_size_exits_nonzero():
     assert p.returncode != 0 and "--gpus 2" in p.stderr and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_outputs_fit_the_budget(tmp_path):
+    """--dump-outputs: the kept tables of the queues' shares become one float64 table in batch field order; a table larger than
+    the budget is cut to whole fields taken in a fixed seeded order, the same on every call."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from fluorosequencingimageanalysis_amd import _native as N
+
+    class Eng:
+        def __init__(self, n_fields, per, seed):
+            r = np.random.default_rng(seed)
+            cnt = r.integers(0, 2 * per, n_fields)
+            rows = np.zeros(int(cnt.sum()), N.ROW_DTYPE)
+            rows["field"] = np.repeat(np.arange(n_fields), cnt)
+            rows["h0"] = r.random(len(rows))
+            self.n_fields = n_fields
+            self.table = torch.from_numpy(rows.view(np.uint8).reshape(-1, 128).copy())
+            self.nkeep = torch.tensor(list(cnt) + [cnt.sum()], dtype=torch.int32)
+            self.counts = torch.tensor(list(9 * cnt) + [0], dtype=torch.int32)
+
+        def kept_table(self):
+            return self.table, None
+
+    fcol = N.ROW_DTYPE.names.index("field")
+    for per, whole in ((5, True), (600, False)):
+        engs = [Eng(341, per, 1), Eng(341, per, 2), Eng(342, per, 3)]
+        out = bench.peak_outputs(engs, [0, 341, 682, 1024], N)
+        again = bench.peak_outputs(engs, [0, 341, 682, 1024], N)
+        assert all(np.array_equal(out[k], again[k]) for k in out)
+        assert sum(v.nbytes for v in out.values()) <= bench.DUMP_BYTES
+        f = out["kept_rows"][:, fcol].astype(np.int64)
+        kept = out["kept_per_field"].astype(np.int64)
+        assert (np.diff(f) >= 0).all() and len(kept) == 1024 and (out["candidates_per_field"] == 9 * kept).all()
+        fields = out["kept_rows_fields"].astype(np.int64)
+        assert (len(fields) == 1024) == whole
+        assert (np.bincount(f, minlength=1024)[fields] == kept[fields]).all()        # the fields dumped are complete
+        assert np.isin(f, fields).all()
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in out)
+    assert np.load(tmp_path / "d" / "kept_rows.npy").dtype == np.float64
+
+
 class _FakeEvent:
     def __init__(self, *a, **k):
         pass
