@@ -406,3 +406,109 @@ class SequenceExperiment(Experiment):
             frame_spots=[image.spots for image in self.peptide_frames], frame_shape=self.peptide_frames[0].image.shape,
             offsets=self.offsets, spot_radius=0)
         return self.spot_traces
+
+
+from .stepfitting import PhotometryTrace, PlateauTrace  # noqa: E402  (flexlibrary.py:1595-1662; re-exported here)
+
+
+class SimpleTrace(object):
+    """A Trace that is a list of Spots (or None) through frames (flexlibrary.py:1536-1593); (h, w) is that of the first
+    non-None Spot."""
+
+    def __init__(self, trace):
+        self.trace = trace
+        for spot in trace:
+            if spot is not None:
+                self.h, self.w = spot.h, spot.w
+                break
+        else:
+            raise Exception("flexlibrary.Trace.trace_hw: this Trace is composed entirely of None's.")
+        self.num_frames = len(trace)
+
+
+class TimetraceExperiment(Experiment):
+    """One field of view filmed continuously (flexlibrary.py:3266-3307): frames (Images), spot_traces (SimpleTraces),
+    step_fits {(h, w): PlateauTrace} and step_fit_intermediates {(h, w): {name: Trace}}."""
+
+    def __init__(self, frames, spot_traces=None, step_fits=None, step_fit_intermediates=None):
+        self.frames = frames
+        self.spot_traces = spot_traces
+        self.step_fits = step_fits
+        self.step_fit_intermediates = {} if step_fit_intermediates is None else step_fit_intermediates
+
+    def lc_create_traces(self, initial_spots=None, search_radius=3.0, s_n_cutoff=3.0):
+        """Tracks initial_spots (default: the Spots of the first frame) through the frames from theirs on by luminosity
+        centroid (flexlibrary.py:3309-3384, fsq_centroid_tracking).  Returns the new self.spot_traces."""
+        first_index = None
+        if initial_spots is not None:
+            parent = initial_spots[0].parent_Image if len(initial_spots) else None
+            for f, frame in enumerate(self.frames):
+                if parent is not None and frame is parent:
+                    first_index = f
+                    break
+            else:
+                raise ValueError("All initial_spots must have the same parent_image, and it must be one of the frames in "
+                                 "this experiment.")
+        elif self.frames[0].spots is not None:
+            initial_spots, first_index = self.frames[0].spots, 0
+        else:
+            raise ValueError("Cannot create traces unless either the first frame does has Spots, or initial_spots are "
+                             "specified via argument.")
+        if not all(s.parent_Image is self.frames[first_index] for s in initial_spots):
+            raise ValueError("All initial_spots must have the same parent_image, and it must be one of the frames in this "
+                             "experiment.")
+        raw = Experiment.luminosity_centroid_particle_tracking(self.frames[first_index:], initial_spots,
+                                                               search_radius=search_radius, s_n_cutoff=s_n_cutoff)
+        for trace in raw:
+            for spot in trace[1:]:                   # (the initial Spots already belong to their Image)
+                if spot is None:
+                    continue
+                if spot.parent_Image.spots is None:
+                    spot.parent_Image.spots = []
+                spot.parent_Image.spots.append(spot)
+        self.spot_traces = [SimpleTrace(trace) for trace in raw]
+        return self.spot_traces
+
+    def stepfit_tracks(self, photometry_min=None, photometry_method='mexican_hat', mirror_start=0, chung_kennedy=0,
+                       p_threshold=0.01, **kwargs):
+        """Step fit of every track's photometries (flexlibrary.py:3449-3530): all mexican-hat photometries in one
+        fsq_mexican_hat call, all traces in one fsq_stepfit_traces call.  Returns and stores (step_fits,
+        step_fit_intermediates), keyed by each track's (h, w); raises if two tracks share one."""
+        from . import photometry as _ph
+        from . import stepfitting as _sf
+        if photometry_method != 'mexican_hat':
+            raise NotImplementedError("stepfit_tracks: only photometry_method='mexican_hat' is built")
+        unknown = set(kwargs) - {"brim_size", "radius", "return_invalid"}
+        if unknown or not kwargs.get("return_invalid", True):
+            raise NotImplementedError("stepfit_tracks: unsupported photometry arguments %s" % sorted(unknown or ["return_invalid"]))
+        brim_size, radius = kwargs.get("brim_size", 6), kwargs.get("radius", 9)
+        traces = list(self.spot_traces or [])
+        keys = []
+        for trace in traces:
+            if (trace.h, trace.w) in keys:
+                raise Exception("Two tracks have initial Spots with identical (h, w).")
+            keys.append((trace.h, trace.w))
+        if not traces:
+            self.step_fits = {}
+            return self.step_fits, self.step_fit_intermediates
+        index = {id(frame): f for f, frame in enumerate(self.frames)}
+        fhw, where = [], []
+        for t, trace in enumerate(traces):
+            for f, spot in enumerate(trace.trace):
+                if spot is not None:
+                    fhw.append((index[id(spot.parent_Image)], spot.h, spot.w))
+                    where.append((t, f))
+        stack = np.stack([np.asarray(fr.image) for fr in self.frames])
+        phot = _ph.mexican_hat_photometry_metric(stack, np.asarray(fhw, np.int64).reshape(-1, 3), brim_size, radius)
+        rows = [[0.0] * trace.num_frames for trace in traces]          # (a None Spot's photometry is 0)
+        for (t, f), v in zip(where, phot.tolist()):
+            rows[t][f] = v
+        fits = _sf.stepfit_photometries(rows, mirror_start=mirror_start, chung_kennedy=chung_kennedy, p_threshold=p_threshold,
+                                        photometry_min=photometry_min, keys=keys)
+        step_fits = {}
+        for key, (ph, ck, pl, tf) in zip(keys, fits):
+            step_fits[key] = tf
+            self.step_fit_intermediates.setdefault(key, {}).update(
+                {'photometries': ph, 'ck_filtered_photometries': ck, 'plateaus': pl, 't_filtered_plateaus': tf})
+        self.step_fits = step_fits
+        return self.step_fits, self.step_fit_intermediates

@@ -1,0 +1,305 @@
+"""Step fitting of spot photometry traces on the GPU (include/fsq_stepfit.h): the live path of the reference's
+Trace.stepfit_photometries (flexlibrary.py:1380-1462) through stepfitting_library, for many traces in one launch.
+
+stepfit_records is the fast path (flat arrays, no Python object per plateau); stepfit_photometries returns the reference's
+4-tuple per trace.  sliding_t_fitter, chung_kennedy_filter, t_test_filter, refit_plateaus and the mirror helpers are
+drop-ins with the reference's names and defaults."""
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+from . import _native_stepfit as NS
+from . import engine as _engine
+
+CK_WINDOW_LENGTHS = (2, 4, 8, 16)     # the live path's CK windows (flexlibrary.py:1436)
+LIVE_WINDOW_RADIUS = 6                 # flexlibrary.py:1439
+
+
+class PhotometryTrace(object):
+    """flexlibrary.PhotometryTrace (flexlibrary.py:1595-1611): a sequence of photometries at (h, w)."""
+
+    def __init__(self, trace, h, w):
+        self.trace = trace
+        self.h, self.w = h, w
+        self.num_frames = len(trace)
+
+    def photometry(self, frame, **kwargs):
+        return self.trace[frame]
+
+    def plateau_starts(self):
+        return set(range(self.num_frames))
+
+
+class PlateauTrace(object):
+    """flexlibrary.PlateauTrace (flexlibrary.py:1630-1662): a list of (start, stop, height) plateaus at (h, w)."""
+
+    def __init__(self, trace, h, w):
+        self.trace = trace
+        self.h, self.w = h, w
+        self.num_frames = trace[-1][1] + 1 if len(trace) > 0 else 0
+
+    def plateau_starts(self):
+        return set(p[0] for p in self.trace)
+
+
+def _as_rows(photometries, photometry_min):
+    """Photometry sequences -> (float64 [n, max_frames] host rows, int32 lengths).  None frames count 0."""
+    if isinstance(photometries, np.ndarray) and photometries.ndim == 2:
+        seqs = [np.asarray(r, dtype=np.float64) for r in photometries]
+    else:
+        seqs = [np.array([0.0 if v is None else float(v) for v in s], dtype=np.float64) for s in photometries]
+    lens = np.array([len(s) for s in seqs], dtype=np.int32)
+    if len(seqs) and lens.min() < 1:
+        raise ValueError("every photometry trace needs at least one frame")
+    max_frames = int(lens.max()) if len(seqs) else 1
+    rows = np.zeros((len(seqs), max_frames), dtype=np.float64)
+    for i, s in enumerate(seqs):
+        if photometry_min is None and np.isnan(s).any():
+            # (the reference's plateau comparisons depend on object identity with NaN heights: no pinnable result)
+            raise ValueError("trace %d holds a NaN photometry; pass photometry_min to clamp it" % i)
+        rows[i, :len(s)] = s
+    return rows, lens
+
+
+def _params(mirror_start, chung_kennedy, p_threshold, photometry_min, window_radius=LIVE_WINDOW_RADIUS, drop_sort=True,
+            window_lengths=CK_WINDOW_LENGTHS, M=10, p=2):
+    if int(mirror_start) < 0:
+        raise ValueError("mirror_size must be greater than 0.")
+    if p != 2:
+        raise NotImplementedError("chung_kennedy_filter: only p = 2 is built")
+    wl = tuple(int(w) for w in window_lengths)
+    if chung_kennedy > 0 and not (1 <= len(wl) <= NS.MAX_WINDOWS and all(1 <= w <= 64 for w in wl) and 1 <= M <= 64):
+        raise NotImplementedError("chung_kennedy_filter: at most %d window lengths in 1..64 and M in 1..64" % NS.MAX_WINDOWS)
+    if not 0 <= int(window_radius) <= 64:
+        raise NotImplementedError("sliding_t_fitter: window_radius above 64 is not built")
+    prm = NS.FsqStepfitParams()
+    prm.mirror_start = int(mirror_start)
+    prm.chung_kennedy = int(chung_kennedy)
+    prm.n_windows = len(wl)
+    for k, w in enumerate(wl[:NS.MAX_WINDOWS]):
+        prm.window_lengths[k] = w
+    prm.M, prm.p = int(M), int(p)
+    prm.window_radius = int(window_radius)
+    prm.drop_sort = 1 if drop_sort else 0
+    prm.p_threshold = float(p_threshold)
+    prm.has_photometry_min = 0 if photometry_min is None else 1
+    prm.photometry_min = 0.0 if photometry_min is None else float(photometry_min)
+    return prm
+
+
+def _check_lengths(lens, prm):
+    mirrored = lens + np.minimum(lens, prm.mirror_start)
+    if len(lens) and mirrored.max() > NS.MAX_MIRRORED:
+        raise ValueError("traces are limited to %d frames after mirroring" % NS.MAX_MIRRORED)
+    if prm.chung_kennedy > 0 and len(lens) and mirrored.min() <= 2:
+        raise ValueError("luminosities must have len(luminosities) > 2 for the Chung-Kennedy filter")
+
+
+def run_device(d_phot, d_len, max_frames, prm, want_p=False, pair_cap=0):
+    """fsq_stepfit_traces on device tensors (float64 [n, max_frames], int32 [n]); returns a dict of device tensors:
+    ck, pl_start, pl_stop, pl_h, pl_n, tf_start, tf_stop, tf_h, tf_n, status (and p when want_p; pair_p [n, pair_cap] and
+    pair_n, the t-filter pair tests, when pair_cap > 0).  Enqueued on the current stream, not synchronised.  Lengths are not
+    checked here: invalid traces come back with status 2."""
+    torch = _engine._torch()
+    dev = d_phot.device
+    n = int(d_phot.shape[0])
+    L = NS.lib()
+    ws_bytes = L.fsq_stepfit_workspace_bytes(n, int(max_frames), ctypes.byref(prm))
+    if ws_bytes < 0:
+        raise ValueError("fsq_stepfit_workspace_bytes: invalid parameters")
+    Lmax = max_frames + min(prm.mirror_start, max_frames)
+    n_radii = max(prm.window_radius - 5, 0)
+    out = {"ck": torch.empty((n, max_frames), dtype=torch.float64, device=dev)}
+    for pre in ("pl", "tf"):
+        out[pre + "_start"] = torch.empty((n, max_frames), dtype=torch.int32, device=dev)
+        out[pre + "_stop"] = torch.empty((n, max_frames), dtype=torch.int32, device=dev)
+        out[pre + "_h"] = torch.empty((n, max_frames), dtype=torch.float64, device=dev)
+        out[pre + "_n"] = torch.empty(n, dtype=torch.int32, device=dev)
+    out["status"] = torch.empty(n, dtype=torch.int32, device=dev)
+    if want_p:
+        out["p"] = torch.empty((n, n_radii, Lmax), dtype=torch.float64, device=dev)
+    if pair_cap > 0:
+        out["pair_p"] = torch.empty((n, pair_cap), dtype=torch.float64, device=dev)
+        out["pair_n"] = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+    o = out
+    rc = L.fsq_stepfit_traces(d_phot.data_ptr(), d_len.data_ptr(), n, int(max_frames), ctypes.byref(prm), o["ck"].data_ptr(),
+                              o["pl_start"].data_ptr(), o["pl_stop"].data_ptr(), o["pl_h"].data_ptr(), o["pl_n"].data_ptr(),
+                              o["tf_start"].data_ptr(), o["tf_stop"].data_ptr(), o["tf_h"].data_ptr(), o["tf_n"].data_ptr(),
+                              o["status"].data_ptr(), o["p"].data_ptr() if want_p else None,
+                              o["pair_p"].data_ptr() if pair_cap > 0 else None, o["pair_n"].data_ptr() if pair_cap > 0 else None,
+                              int(pair_cap), ws.data_ptr(), int(ws_bytes),
+                              torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_stepfit_traces")
+    out["_ws"] = ws                   # (kept alive until the caller has read the outputs)
+    return out
+
+
+def _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min, want_p=False, device=None, **kw):
+    prm = _params(mirror_start, chung_kennedy, p_threshold, photometry_min, **kw)
+    rows, lens = _as_rows(photometries, photometry_min)
+    _check_lengths(lens, prm)
+    if len(lens) == 0:
+        return None, lens, prm
+    torch = _engine._torch()
+    dev = torch.device(device or "cuda")
+    d_phot = torch.from_numpy(rows).to(dev)
+    d_len = torch.from_numpy(lens).to(dev)
+    out = run_device(d_phot, d_len, rows.shape[1], prm, want_p=want_p)
+    host = {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+    st = host["status"]
+    if (st == NS.STATUS_UNSUPPORTED).any():
+        raise NotImplementedError("trace %d: a t-filter pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
+                                  "is not restated)" % int(np.flatnonzero(st == NS.STATUS_UNSUPPORTED)[0]))
+    if (st != NS.STATUS_OK).any():
+        raise ValueError("trace %d: invalid length" % int(np.flatnonzero(st != NS.STATUS_OK)[0]))
+    host["rows"], host["lens"] = rows, lens
+    return host, lens, prm
+
+
+def _flat(host, pre):
+    cnt = host[pre + "_n"].astype(np.int64)
+    mask = np.arange(host[pre + "_start"].shape[1])[None, :] < cnt[:, None]
+    trace = np.nonzero(mask)[0].astype(np.int64)
+    return {"trace": trace, "start": host[pre + "_start"][mask], "stop": host[pre + "_stop"][mask], "height": host[pre + "_h"][mask],
+            "counts": cnt}
+
+
+def stepfit_records(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, photometry_min=None, device=None):
+    """Trace.stepfit_photometries for many traces, as flat arrays.
+
+    Returns a dict: "plateaus" and "t_filtered_plateaus", each {"trace", "start", "stop", "height", "counts"} (one entry per
+    plateau, in trace order; counts per trace), "ck_filtered" (float64 [n, max_frames], row t valid for its own length)
+    and "lengths"."""
+    host, lens, prm = _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min, device=device)
+    if host is None:
+        empty = {"trace": np.zeros(0, np.int64), "start": np.zeros(0, np.int32), "stop": np.zeros(0, np.int32),
+                 "height": np.zeros(0), "counts": np.zeros(0, np.int64)}
+        return {"plateaus": empty, "t_filtered_plateaus": dict(empty), "ck_filtered": np.zeros((0, 1)), "lengths": lens}
+    return {"plateaus": _flat(host, "pl"), "t_filtered_plateaus": _flat(host, "tf"), "ck_filtered": host["ck"], "lengths": lens}
+
+
+def _plateau_lists(host, pre, i):
+    n = int(host[pre + "_n"][i])
+    s, o, h = host[pre + "_start"][i, :n].tolist(), host[pre + "_stop"][i, :n].tolist(), host[pre + "_h"][i, :n]
+    return [(s[k], o[k], np.float64(h[k])) for k in range(n)]
+
+
+def stepfit_photometries(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, photometry_min=None, keys=None,
+                         device=None):
+    """Trace.stepfit_photometries (flexlibrary.py:1380-1462) for every sequence of `photometries` (a 2-D array or a list of
+    ragged sequences).  Returns one (photometries, ck_filtered_photometries, plateaus, t_filtered_plateaus) tuple per trace:
+    PhotometryTrace, PhotometryTrace, PlateauTrace, PlateauTrace, at keys[i] = (h, w) (None when keys is None)."""
+    host, lens, prm = _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min, device=device)
+    if host is None:
+        return []
+    if keys is not None and len(keys) != len(lens):
+        raise ValueError("keys must hold one (h, w) per trace")
+    res = []
+    rows, ck = host["rows"], host["ck"]
+    m = int(mirror_start)
+    for i, n in enumerate(lens.tolist()):
+        h, w = keys[i] if keys is not None else (None, None)
+        ph = rows[i, :n]
+        if photometry_min is not None:
+            ph = np.where(ph > photometry_min, ph, photometry_min)
+        nck = max(n + min(m, n) - m, 0)
+        res.append((PhotometryTrace(tuple(ph.tolist()), h, w), PhotometryTrace(ck[i, :nck].tolist(), h, w),
+                    PlateauTrace(_plateau_lists(host, "pl", i), h, w), PlateauTrace(_plateau_lists(host, "tf", i), h, w)))
+    return res
+
+
+# ---- drop-ins of stepfitting_library ----------------------------------------------------------------------------------
+def sliding_t_fitter(luminosity_sequence, window_radius=20, p_threshold=0.001, median_filter_size=None, downsteps_only=False,
+                     min_step_magnitude=None):
+    """stepfitting_library.sliding_t_fitter (:929-1078) on the GPU."""
+    if median_filter_size is not None or downsteps_only or min_step_magnitude is not None:
+        raise NotImplementedError("sliding_t_fitter: median_filter_size, downsteps_only and min_step_magnitude are not built")
+    host, _, _ = _run([luminosity_sequence], 0, 0, p_threshold, None, window_radius=window_radius)
+    return _plateau_lists(host, "pl", 0)
+
+
+def chung_kennedy_filter(luminosities, window_lengths=range(2, 17), M=10, p=2):
+    """stepfitting_library.chung_kennedy_filter (:1081-1274) on the GPU."""
+    if not len(luminosities) > 2:
+        raise ValueError("luminosities must have len(luminosities) > 2; currently len(luminosities) = " + str(len(luminosities)))
+    host, lens, _ = _run([luminosities], 0, 1, 0.01, None, window_lengths=tuple(window_lengths), M=M, p=p, window_radius=0)
+    return host["ck"][0, :int(lens[0])].tolist()
+
+
+def t_test_filter(luminosities, plateaus, p_threshold, drop_sort=True, no_merge_start=0):
+    """stepfitting_library.t_test_filter (:1441-1480) on the GPU (fsq_stepfit_ttest_filter): merges adjacent plateaus whose
+    Welch t-test p >= p_threshold, len(plateaus) - 1 passes, both the drop_sort and the left-to-right branch.  Plateaus
+    must be consecutive (stop + 1 == next start) within the luminosities; unmerged plateaus keep their given heights."""
+    lum = np.array([0.0 if v is None else float(v) for v in luminosities], dtype=np.float64)
+    pls = [(int(a), int(o), float(h)) for a, o, h in plateaus]
+    if len(pls) < 2:
+        return list(plateaus)
+    n = len(lum)
+    if n > NS.MAX_MIRRORED:
+        raise ValueError("t_test_filter: at most %d luminosities" % NS.MAX_MIRRORED)
+    if not (0 <= pls[0][0] and pls[-1][1] < n and all(a <= o for a, o, _ in pls) and
+            all(pls[i][1] + 1 == pls[i + 1][0] for i in range(len(pls) - 1))):
+        raise ValueError("Merged plateaus must be consecutive and lie within the luminosities")
+    torch = _engine._torch()
+    dev = torch.device("cuda")
+    L = NS.lib()
+    ws_bytes = L.fsq_stepfit_ttest_filter_workspace_bytes(1, n)
+    st = np.zeros((1, n), np.int32); so = np.zeros((1, n), np.int32); hh = np.zeros((1, n))
+    st[0, :len(pls)] = [a for a, _, _ in pls]; so[0, :len(pls)] = [o for _, o, _ in pls]; hh[0, :len(pls)] = [h for _, _, h in pls]
+    d = {k: torch.from_numpy(v).to(dev) for k, v in (("lum", lum[None]), ("len", np.array([n], np.int32)), ("s", st), ("o", so),
+                                                       ("h", hh), ("n", np.array([len(pls)], np.int32)))}
+    out = {"s": torch.empty((1, n), dtype=torch.int32, device=dev), "o": torch.empty((1, n), dtype=torch.int32, device=dev),
+           "h": torch.empty((1, n), dtype=torch.float64, device=dev), "n": torch.empty(1, dtype=torch.int32, device=dev),
+           "st": torch.empty(1, dtype=torch.int32, device=dev)}
+    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+    rc = L.fsq_stepfit_ttest_filter(d["lum"].data_ptr(), d["len"].data_ptr(), 1, n, d["s"].data_ptr(), d["o"].data_ptr(),
+                                    d["h"].data_ptr(), d["n"].data_ptr(), float(p_threshold), 1 if drop_sort else 0,
+                                    int(no_merge_start), out["s"].data_ptr(), out["o"].data_ptr(), out["h"].data_ptr(),
+                                    out["n"].data_ptr(), out["st"].data_ptr(), None, None, 0, ws.data_ptr(), int(ws_bytes),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_stepfit_ttest_filter")
+    h = {k: v.cpu().numpy() for k, v in out.items()}
+    if h["st"][0] == NS.STATUS_UNSUPPORTED:
+        raise NotImplementedError("t_test_filter: a pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
+                                  "is not restated)")
+    if h["st"][0] != NS.STATUS_OK:
+        raise ValueError("t_test_filter: invalid plateaus")
+    k = int(h["n"][0])
+    return [(int(h["s"][0, i]), int(h["o"][0, i]), np.float64(h["h"][0, i])) for i in range(k)]
+
+
+def refit_plateaus(luminosities, plateaus):
+    """stepfitting_library.refit_plateaus (:1322): np.mean of each plateau's frames."""
+    lum = np.asarray(luminosities, dtype=np.float64)
+    out = []
+    for start, stop, height in plateaus:
+        if not 0 <= start <= stop < len(lum):
+            raise ValueError("Invalid (starting_frame, stopping_frame): " + str((start, stop)))
+        out.append((start, stop, np.mean(lum[start:stop + 1])))
+    return out
+
+
+def mirror_photometries(photometries, mirror_size):
+    if mirror_size < 0:
+        raise ValueError("mirror_size must be greater than 0.")
+    return [x for x in reversed(photometries[:mirror_size])] + list(photometries)
+
+
+def unmirror_photometries(photometries, mirror_size):
+    if mirror_size < 0:
+        raise ValueError("mirror_size must be greater than 0.")
+    return photometries[mirror_size:]
+
+
+def unmirror_plateaus(plateaus, mirror_size):
+    if mirror_size < 0:
+        raise ValueError("mirror_size must be greater than 0.")
+    out = []
+    for a, o, h in plateaus:
+        a, o = a - mirror_size, o - mirror_size
+        if a < 0 and o < 0:
+            continue
+        out.append((max(a, 0), o, h))
+    return out

@@ -1,0 +1,244 @@
+"""Step fit on the GPU (fsq_stepfit_traces): bit for bit against the reference's recorded outputs, p within 1e-10 of scipy,
+and random traces against the NumPy restatement (tests/_stepfit_reference.py)."""
+import numpy as np
+import pytest
+
+import _stepfit_reference as R
+from test_stepfit_host import _bits, check_pair_p, golden_cases, timetrace_golden
+
+pytestmark = pytest.mark.gpu
+
+
+def _same_plateaus(got, exp):
+    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp]
+    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp]))
+
+
+def _run_case(c, want_p=False):
+    import torch
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    prm = S._params(c["mirror"], c["ck"], c["thr"], c["pmin"], window_radius=c["wr"], drop_sort=c["drop_sort"])
+    rows, lens = S._as_rows([c["phot"].tolist()], c["pmin"])
+    out = S.run_device(torch.from_numpy(rows).cuda(), torch.from_numpy(lens).cuda(), rows.shape[1], prm, want_p=want_p)
+    return {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+
+
+def test_golden_through_c_abi():
+    for i, c in enumerate(golden_cases()):
+        h = _run_case(c, want_p=True)
+        assert h["status"][0] == 0, i
+        n = len(c["phot"])
+        nck = len(c["ck_out"])
+        assert np.array_equal(_bits(h["ck"][0, :nck]), _bits(c["ck_out"])), i
+        for pre, key in (("pl", "pl"), ("tf", "tf")):
+            k = int(h[pre + "_n"][0])
+            got = list(zip(h[pre + "_start"][0, :k], h[pre + "_stop"][0, :k], h[pre + "_h"][0, :k]))
+            _same_plateaus(got, c[key])
+        Lm = n + min(c["mirror"], n)
+        n_radii = max(c["wr"] - 5, 0)
+        p = h["p"][0][:, :Lm].reshape(-1) if n_radii else np.zeros(0)
+        exp = c["p_slide"]
+        assert p.shape == exp.shape, i
+        assert np.array_equal(np.isnan(p), np.isnan(exp)), i
+        assert np.array_equal(p == 0, exp == 0), i
+        f = np.isfinite(exp) & (exp != 0)
+        rel = np.abs(p[f] - exp[f]) / np.abs(exp[f])
+        assert rel.size == 0 or rel.max() <= 1e-10, (i, rel.max())
+
+
+def test_golden_through_python_api():
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    for i, c in enumerate(golden_cases()):
+        if c["wr"] != 6 or not c["drop_sort"]:
+            continue                                  # (the live path: window_radius 6, drop_sort)
+        (ph, ck, pl, tf), = S.stepfit_photometries([c["phot"].tolist()], mirror_start=c["mirror"], chung_kennedy=c["ck"],
+                                                   p_threshold=c["thr"], photometry_min=c["pmin"], keys=[(4, 5)])
+        assert (ph.h, ph.w, tf.h, tf.w) == (4, 5, 4, 5)
+        assert np.array_equal(_bits(ph.trace), _bits(c["phot_out"])), i
+        assert np.array_equal(_bits(ck.trace), _bits(c["ck_out"])), i
+        _same_plateaus(pl.trace, c["pl"])
+        _same_plateaus(tf.trace, c["tf"])
+
+
+def test_golden_records_batch():
+    """All live-path goldens with the same parameters in one launch, through stepfit_records."""
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    cases = [c for c in golden_cases() if c["wr"] == 6 and c["drop_sort"] and c["mirror"] == 3 and c["thr"] == 0.01
+             and c["pmin"] is None]
+    for ck in (0, 1):
+        sel = [c for c in cases if (c["ck"] > 0) == bool(ck)]
+        r = S.stepfit_records([c["phot"].tolist() for c in sel], mirror_start=3, chung_kennedy=ck, p_threshold=0.01)
+        for key in ("plateaus", "t_filtered_plateaus"):
+            t = r[key]
+            for j, c in enumerate(sel):
+                m = t["trace"] == j
+                _same_plateaus(list(zip(t["start"][m], t["stop"][m], t["height"][m])), c["pl" if key == "plateaus" else "tf"])
+
+
+def _random_traces(rng, n_traces, max_len):
+    out = []
+    for _ in range(n_traces):
+        n = int(rng.integers(1, max_len + 1))
+        nf = int(rng.integers(0, 5))
+        lvl = np.full(n, float(nf))
+        for _k in range(nf):
+            lvl[int(rng.integers(0, n)):] -= 1
+        v = lvl * rng.uniform(5e3, 3e4) + rng.normal(0, rng.uniform(1e3, 6e3), n)
+        v = np.round(v * 2) / 2 if rng.random() < 0.5 else np.round(v)
+        if rng.random() < 0.2:
+            v[rng.random(n) < 0.1] = 0.0
+        out.append(v)
+    return out
+
+
+def _check_sample(traces, idx, r, opts):
+    checked = 0
+    for j in idx:
+        ph, ck, pl, tf, fl = R.stepfit(traces[j].tolist(), **opts)
+        if fl.near or fl.unsupported:
+            continue
+        t = r["ck_filtered"][j, :len(ck)]
+        assert np.array_equal(_bits(t), _bits(ck)), j
+        for key, exp in (("plateaus", pl), ("t_filtered_plateaus", tf)):
+            T = r[key]
+            m = T["trace"] == j
+            _same_plateaus(list(zip(T["start"][m], T["stop"][m], T["height"][m])), exp)
+        checked += 1
+    return checked
+
+
+@pytest.mark.parametrize("mirror,ck,thr,pmin", [(0, 0, 0.01, None), (3, 1, 0.01, None), (7, 2, 0.001, None),
+                                                (3, 0, 0.01, 0.0), (3, 1, 0.001, 0.0)])
+def test_random_traces_equal_restatement(mirror, ck, thr, pmin):
+    """2 000 ragged traces (1 - 1000 frames) per option set in one launch (10 000 in all); a sample of 300 per set is
+    restated on the host (the restatement runs a Python loop per frame)."""
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    rng = np.random.default_rng(1000 + 10 * mirror + ck)
+    traces = _random_traces(rng, 2000, 1000)
+    if ck:
+        traces = [t if len(t) + min(mirror, len(t)) > 2 else np.concatenate([t, [1.0, 2.0, 3.0]]) for t in traces]
+    r = S.stepfit_records(traces, mirror_start=mirror, chung_kennedy=ck, p_threshold=thr, photometry_min=pmin)
+    assert len(r["plateaus"]["counts"]) == 2000
+    idx = rng.choice(2000, 300, replace=False)
+    n = _check_sample(traces, idx, r, dict(mirror_start=mirror, chung_kennedy=ck, p_threshold=thr, photometry_min=pmin))
+    assert n >= 250
+
+
+def test_large_batch_sampled():
+    """65 536 traces x 256 frames (the benchmark's shape) in one launch, sampled against the restatement."""
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    rng = np.random.default_rng(5)
+    base = _random_traces(rng, 256, 256)
+    base = [np.resize(t, 256) for t in base]
+    rows = np.stack([base[i % 256] + (i // 256) for i in range(65536)])
+    for ck in (0, 1):
+        r = S.stepfit_records(rows, mirror_start=3, chung_kennedy=ck, p_threshold=0.01)
+        idx = rng.choice(65536, 60, replace=False)
+        assert _check_sample(list(rows), idx, r, dict(mirror_start=3, chung_kennedy=ck, p_threshold=0.01)) >= 50
+
+
+def test_drop_ins():
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    rng = np.random.default_rng(3)
+    v = _random_traces(rng, 1, 200)[0]
+    v = np.concatenate([v, [3e4] * 30])
+    fl = R.Flags()
+    steps = R.sliding_steps(v, 20, 0.001, fl)
+    if not fl.near:
+        _same_plateaus(S.sliding_t_fitter(v.tolist()), R.plateaus_from_steps(steps, len(v), v))
+    exp = R.ck_filter(v.tolist(), window_lengths=tuple(range(2, 17)))
+    assert np.array_equal(_bits(S.chung_kennedy_filter(v.tolist())), _bits(exp))
+
+
+def test_golden_pair_p_within_tolerance():
+    """p of every t-filter pair test (long plateaus: large df) against scipy's recorded values."""
+    import torch
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    for i, c in enumerate(golden_cases()):
+        prm = S._params(c["mirror"], c["ck"], c["thr"], c["pmin"], window_radius=c["wr"], drop_sort=c["drop_sort"])
+        rows, lens = S._as_rows([c["phot"].tolist()], c["pmin"])
+        cap = max(len(c["p_pairs"]), 1)
+        out = S.run_device(torch.from_numpy(rows).cuda(), torch.from_numpy(lens).cuda(), rows.shape[1], prm, pair_cap=cap)
+        k = int(out["pair_n"][0].item())
+        check_pair_p(out["pair_p"][0, :k].cpu().numpy(), c["p_pairs"])
+
+
+def test_timetrace_experiment_golden():
+    """TimetraceExperiment.lc_create_traces + stepfit_tracks with the script's defaults, end to end."""
+    from fluorosequencingimageanalysis_amd import flexlibrary as F
+    g = timetrace_golden()
+    imgs = [F.Image(image=f) for f in g["frames"]]
+    spots = [F.Spot(imgs[0], int(h), int(w), 5) for h, w in g["init_hw"]]
+    ex = F.TimetraceExperiment(imgs)
+    ex.lc_create_traces(initial_spots=spots, search_radius=3.0)
+    step_fits, inter = ex.stepfit_tracks()
+    assert [tuple(k) for k in g["keys"].tolist()] == list(step_fits.keys())
+    for k, key in enumerate(step_fits.keys()):
+        d = inter[key]
+        assert d["t_filtered_plateaus"] is step_fits[key]
+        assert np.array_equal(_bits(d["photometries"].trace), _bits(g["photometries"][k]))
+        assert np.array_equal(_bits(d["ck_filtered_photometries"].trace), _bits(g["ck_filtered"][k]))
+        for pre, name in (("pl", "plateaus"), ("tf", "t_filtered_plateaus")):
+            m = g[pre + "_trace"] == k
+            _same_plateaus(d[name].trace, list(zip(g[pre + "_start"][m], g[pre + "_stop"][m], g[pre + "_h"][m])))
+        assert (d["plateaus"].h, d["plateaus"].w) == key
+
+
+@pytest.mark.parametrize("drop_sort", [True, False])
+def test_t_test_filter_drop_in(drop_sort):
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    rng = np.random.default_rng(11 + drop_sort)
+    checked = 0
+    for tr in _random_traces(rng, 150, 400):
+        n = len(tr)
+        cuts = sorted(set(rng.integers(1, n, int(rng.integers(0, 12))).tolist())) if n > 1 else []
+        b = [0] + cuts + [n]
+        pl = [(b[i], b[i + 1] - 1, float(np.mean(tr[b[i]:b[i + 1]])) + 0.25) for i in range(len(b) - 1)]
+        nms = int(rng.integers(0, 8))
+        fl = R.Flags()
+        exp = R.t_test_filter(tr, pl, 0.01, drop_sort=drop_sort, no_merge_start=nms, flags=fl)
+        if fl.near or exp is None:
+            continue
+        _same_plateaus(S.t_test_filter(tr.tolist(), pl, 0.01, drop_sort=drop_sort, no_merge_start=nms), exp)
+        checked += 1
+    assert checked >= 120
+
+
+def test_unsupported_sort_raises():
+    """66 equal constant plateaus: every pair p is NaN and a pass sorts 65 pairs -> FSQ_STEPFIT_UNSUPPORTED."""
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    pl = [(2 * i, 2 * i + 1, 5.0) for i in range(66)]
+    with pytest.raises(NotImplementedError):
+        S.t_test_filter([5.0] * 132, pl, 0.01)
+    # fewer than 64 pairs with NaN keys: the CPython order is restated and nothing merges (NaN never passes >=)
+    assert S.t_test_filter([5.0] * 40, pl[:20], 0.01) == [(a, o, h) for a, o, h in pl[:20]]
+
+
+@pytest.mark.parametrize("wr,drop_sort,nan", [(20, True, False), (6, False, False), (20, False, True), (6, True, True)])
+def test_random_traces_other_options(wr, drop_sort, nan):
+    """window_radius 20, drop_sort False and NaN photometries clamped by photometry_min, against the restatement."""
+    import torch
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    rng = np.random.default_rng(wr * 10 + drop_sort * 2 + nan)
+    traces = _random_traces(rng, 1000, 600)
+    pmin = -500.0 if nan else None
+    if nan:
+        for t in traces:
+            t[rng.random(len(t)) < 0.03] = np.nan
+    traces = [t if len(t) + min(3, len(t)) > 2 else np.concatenate([t, [1.0, 2.0, 3.0]]) for t in traces]
+    prm = S._params(3, 1, 0.01, pmin, window_radius=wr, drop_sort=drop_sort)
+    rows, lens = S._as_rows(traces, pmin)
+    out = S.run_device(torch.from_numpy(rows).cuda(), torch.from_numpy(lens).cuda(), rows.shape[1], prm)
+    h = {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+    checked = 0
+    for j in rng.choice(len(traces), 120, replace=False):
+        ph, ck, pl, tf, fl = R.stepfit(traces[j].tolist(), 3, 1, 0.01, pmin, window_radius=wr, drop_sort=drop_sort)
+        if fl.near or fl.unsupported:
+            continue
+        assert h["status"][j] == 0
+        assert np.array_equal(_bits(h["ck"][j, :len(ck)]), _bits(ck))
+        for pre, exp in (("pl", pl), ("tf", tf)):
+            k = int(h[pre + "_n"][j])
+            _same_plateaus(list(zip(h[pre + "_start"][j, :k], h[pre + "_stop"][j, :k], h[pre + "_h"][j, :k])), exp)
+        checked += 1
+    assert checked >= 90

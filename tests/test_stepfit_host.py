@@ -1,0 +1,195 @@
+"""Step fit, host side: the NumPy restatement against the reference's recorded outputs, the CPython sort restatement, the
+C ABI declarations and argument validation (no GPU needed)."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _stepfit_reference as R
+from _util import GOLD, ROOT
+
+
+def golden_cases():
+    g = np.load(os.path.join(GOLD, "stepfit_traces.npz"))
+    out = []
+    for i in range(len(g["case_len"])):
+        def part(k):
+            return g[k][g[k + "_off"][i]:g[k + "_off"][i + 1]]
+
+        def tab(pre):
+            m = g[pre + "_trace"] == i
+            return list(zip(g[pre + "_start"][m].tolist(), g[pre + "_stop"][m].tolist(), g[pre + "_h"][m].tolist()))
+        out.append(dict(phot=part("phot"), phot_out=part("phot_out"), ck_out=part("ck_out"), p_slide=part("p_slide"),
+                        p_pairs=part("p_pairs"),
+                        pl=tab("pl"), tf=tab("tf"), mirror=int(g["case_mirror"][i]), ck=int(g["case_ck"][i]),
+                        wr=int(g["case_wr"][i]), drop_sort=bool(g["case_drop_sort"][i]), thr=float(g["case_thr"][i]),
+                        pmin=float(g["case_pmin"][i]) if g["case_has_min"][i] else None))
+    return out
+
+
+def _bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+
+def test_restatement_bit_identical_to_golden():
+    for i, c in enumerate(golden_cases()):
+        ph, ck, pl, tf, fl = R.stepfit(c["phot"].tolist(), c["mirror"], c["ck"], c["thr"], c["pmin"], window_radius=c["wr"],
+                                       drop_sort=c["drop_sort"])
+        assert not fl.near and not fl.unsupported, i
+        assert np.array_equal(_bits(ph), _bits(c["phot_out"])), i
+        assert np.array_equal(_bits(ck), _bits(c["ck_out"])), i
+        for got, exp in ((pl, c["pl"]), (tf, c["tf"])):
+            assert [(s, o) for s, o, _ in got] == [(s, o) for s, o, _ in exp], i
+            assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp])), i
+
+
+def test_restatement_p_matches_scipy():
+    for i, c in enumerate(golden_cases()):
+        fl = R.Flags()
+        mir = R.stepfit(c["phot"].tolist(), c["mirror"], 0, c["thr"], c["pmin"], window_radius=0)[0]
+        mir = [x for x in reversed(mir[:c["mirror"]])] + list(mir)
+        seq = R.ck_filter(mir) if c["ck"] else mir
+        R.sliding_steps(seq, c["wr"], c["thr"], fl)
+        got = np.array([p for _, _, p in sorted(fl.p_slide, key=lambda x: (x[0], x[1]))])   # (radius, frame) order
+        exp = c["p_slide"]
+        assert got.shape == exp.shape, i
+        assert np.array_equal(np.isnan(got), np.isnan(exp)), i
+        assert np.array_equal(got == 0, exp == 0), i
+        f = np.isfinite(exp) & (exp != 0)
+        assert np.all(np.abs(got[f] - exp[f]) <= 1e-10 * np.abs(exp[f])), i
+
+
+def test_cpython_sort_restatement():
+    rng = np.random.default_rng(7)
+    for _ in range(3000):
+        n = int(rng.integers(0, 64))
+        keys = rng.choice([0.1, 0.2, 0.5, math.nan, 0.9, 0.0], n).tolist() if rng.random() < 0.5 else rng.random(n).tolist()
+        for j in range(n):
+            if rng.random() < 0.2:
+                keys[j] = math.nan
+        assert R.cpython_sort_desc(keys) == sorted(range(n), key=keys.__getitem__, reverse=True)
+
+
+def test_header_matches_binding_and_library():
+    from fluorosequencingimageanalysis_amd import _native, _native_stepfit
+    hdr = open(os.path.join(ROOT, "include", "fsq_stepfit.h")).read()
+    declared = set(re.findall(r"\b(fsq_[a-z_0-9]+)\s*\(", hdr))
+    assert declared == set(_native_stepfit.EXPORTED)
+    if not os.path.exists(_native.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    for name in declared:
+        getattr(L, name)
+    # the params struct has the header's layout: 23 int32, double at 96, int32 at 104, double at 112
+    P = _native_stepfit.FsqStepfitParams
+    assert (P.p_threshold.offset, P.has_photometry_min.offset, P.photometry_min.offset, ctypes.sizeof(P)) == (96, 104, 112, 120)
+
+
+def test_workspace_bytes_validates():
+    from fluorosequencingimageanalysis_amd import _native_stepfit as NS
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    L = NS.lib()
+    prm = S._params(3, 1, 0.01, None)
+    assert L.fsq_stepfit_workspace_bytes(1000, 256, ctypes.byref(prm)) > 0
+    assert L.fsq_stepfit_workspace_bytes(1000, 9000, ctypes.byref(prm)) < 0
+    prm.p = 3
+    assert L.fsq_stepfit_workspace_bytes(1000, 256, ctypes.byref(prm)) < 0
+
+
+def test_argument_validation():
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    with pytest.raises(ValueError):
+        S._check_lengths(np.array([2], np.int32), S._params(0, 1, 0.01, None))
+    with pytest.raises(ValueError):
+        S._check_lengths(np.array([8000], np.int32), S._params(300, 0, 0.01, None))
+    S._check_lengths(np.array([3], np.int32), S._params(0, 1, 0.01, None))
+    with pytest.raises(NotImplementedError):
+        S._params(0, 1, 0.01, None, p=3)
+    with pytest.raises(NotImplementedError):
+        S.sliding_t_fitter([1.0] * 20, median_filter_size=3)
+    with pytest.raises(NotImplementedError):
+        S.sliding_t_fitter([1.0] * 20, downsteps_only=True)
+    with pytest.raises(NotImplementedError):
+        S.sliding_t_fitter([1.0] * 20, min_step_magnitude=5.0)
+    with pytest.raises(NotImplementedError):
+        S.chung_kennedy_filter([1.0] * 20, p=3)
+    with pytest.raises(ValueError):
+        S.chung_kennedy_filter([1.0, 2.0])
+    with pytest.raises(ValueError):
+        S._as_rows([[1.0, math.nan, 2.0]], None)
+    with pytest.raises(ValueError):
+        S._as_rows([[]], None)
+    rows, lens = S._as_rows([[1.0, math.nan, None]], 0.0)
+    assert lens.tolist() == [3] and rows[0, 2] == 0.0
+
+
+def test_restatement_unsupported_flag():
+    # 65 plateaus whose pairs include constant equal plateaus (p = nan): the >= 64-pairs-with-NaN case is flagged
+    pl = [(2 * i, 2 * i + 1, 5.0) for i in range(66)]
+    lum = [5.0] * 132
+    fl = R.Flags()
+    assert R.t_test_filter(lum, pl, 0.01, flags=fl) is None and fl.unsupported
+
+
+def check_pair_p(got, exp):
+    """t-filter pair p in test order against scipy's recorded ones.  The reference runs len(plateaus) - 1 passes; passes
+    after the first one that merges nothing repeat it exactly, and the path stops there - so `got` is a prefix of `exp`
+    that covers every distinct test, and what follows it in `exp` repeats its last pass."""
+    got, exp = np.asarray(got, np.float64), np.asarray(exp, np.float64)
+    assert len(got) <= len(exp)
+    e = exp[:len(got)]
+    assert np.array_equal(np.isnan(got), np.isnan(e))
+    assert np.array_equal(got == 0, e == 0)
+    f = np.isfinite(e) & (e != 0)
+    rel = np.abs(got[f] - e[f]) / np.abs(e[f])
+    assert rel.size == 0 or rel.max() <= 1e-10, rel.max()
+
+
+def test_restatement_pair_p_matches_scipy():
+    for i, c in enumerate(golden_cases()):
+        ph, ck, pl, tf, fl = R.stepfit(c["phot"].tolist(), c["mirror"], c["ck"], c["thr"], c["pmin"], window_radius=c["wr"],
+                                       drop_sort=c["drop_sort"])
+        check_pair_p(fl.p_pairs, c["p_pairs"])
+
+
+def timetrace_golden():
+    return np.load(os.path.join(GOLD, "stepfit_timetrace.npz"))
+
+
+def test_restatement_equals_timetrace_golden():
+    """The recorded photometries of the end-to-end golden, step-fitted by the restatement with the script's defaults."""
+    g = timetrace_golden()
+    for k in range(len(g["keys"])):
+        ph, ck, pl, tf, fl = R.stepfit(g["photometries"][k].tolist())
+        assert not fl.near
+        assert np.array_equal(_bits(ck), _bits(g["ck_filtered"][k]))
+        for got, pre in ((pl, "pl"), (tf, "tf")):
+            m = g[pre + "_trace"] == k
+            assert [(s, o) for s, o, _ in got] == list(zip(g[pre + "_start"][m].tolist(), g[pre + "_stop"][m].tolist()))
+            assert np.array_equal(_bits([h for _, _, h in got]), _bits(g[pre + "_h"][m]))
+
+
+def test_stepfit_tracks_validation():
+    from fluorosequencingimageanalysis_amd import flexlibrary as F
+    ex = F.TimetraceExperiment([F.Image(image=np.zeros((32, 32), np.uint16))])
+    ex.spot_traces = []
+    with pytest.raises(NotImplementedError):
+        ex.stepfit_tracks(photometry_method='sextractor')
+    with pytest.raises(NotImplementedError):
+        ex.stepfit_tracks(scaling=3)
+    assert ex.stepfit_tracks() == ({}, {})
+    with pytest.raises(ValueError):
+        ex.lc_create_traces(initial_spots=[F.Spot(F.Image(image=np.zeros((32, 32), np.uint16)), 10, 10, 5)])
+
+
+def test_t_test_filter_validation():
+    from fluorosequencingimageanalysis_amd import stepfitting as S
+    assert S.t_test_filter([1.0, 2.0], [(0, 1, 1.5)], 0.01) == [(0, 1, 1.5)]
+    with pytest.raises(ValueError):
+        S.t_test_filter([1.0] * 10, [(0, 3, 1.0), (5, 9, 1.0)], 0.01)       # not consecutive
+    with pytest.raises(ValueError):
+        S.t_test_filter([1.0] * 10, [(0, 3, 1.0), (4, 10, 1.0)], 0.01)      # beyond the luminosities
