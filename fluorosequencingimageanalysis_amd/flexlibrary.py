@@ -7,7 +7,12 @@ the GPU from the peak tables:
 
 Same names, arguments, return shapes and exceptions; `track_fields` is the batch form (many fields per launch) that
 works directly on `(h, w)` tables such as the dict keys pflib.find_peptides returns.  The arithmetic is in
-csrc/fsq_track.hip (fsq_greedy_tracking of include/fsq.h); there is no CPU fallback."""
+csrc/fsq_track.hip (fsq_greedy_tracking of include/fsq.h); there is no CPU fallback.
+
+The sequence classes (SequenceExperiment, MultichannelSequenceExperiment, MultifieldMultichannelSequenceExperiment:
+flexlibrary.py:1680-2231, 2471-3263) reduce the tracks to ON/OFF patterns and photometries and write the two CSV files of
+basic_experiment_script; all their traces go through one fsq_sequence_photometry launch (sequencing.py,
+include/fsq_sequence.h)."""
 import ctypes
 
 import numpy as np
@@ -195,6 +200,21 @@ class Spot(object):
             return default
         return float(scaling) * self.gaussian_fit[3] * self.gaussian_fit[4] * self.gaussian_fit[5]
 
+    def photometry(self, method='mexican_hat', photometry_method=None, return_invalid=True, **kwargs):
+        """The Spot's photometry by the named method; None if return_invalid is False and the window leaves the image.
+        flexlibrary.py:286-317.  sextractor, maximum and sigmas need photutils / are not built."""
+        if photometry_method is not None:
+            method = photometry_method
+        if method == 'mexican_hat':
+            return self.mexican_hat_photometry_metric(return_invalid=return_invalid, **kwargs)
+        if method == 'gaussian_volume':
+            return self.gaussian_volume_photometry_metric(return_invalid=return_invalid, **kwargs)
+        if method == 'simple':
+            return self.simple_photometry_metric(return_invalid=return_invalid, **kwargs)
+        if method in ('sextractor', 'maximum', 'sigmas'):
+            raise NotImplementedError("photometry method %r is not built" % (method,))
+        raise ValueError("Uknown method specified.")
+
     def illumina_s_n(self):
         """pflib.illumina_s_n of the Spot's pixels.  flexlibrary.py:319-320."""
         from . import pflib as _pf
@@ -313,6 +333,41 @@ class Experiment(object):
         return tracks
 
     @staticmethod
+    def easy_sort_target_images(filepath_list):
+        """Sort image files by field of view and order taken: every directory is one experimental cycle (directories in
+        sorted order), the sorted file names of a directory are its fields.  flexlibrary.py:1106-1154.
+        Returns (frame_indexed {cycle: [absolute paths, one per field]}, field_indexed {field: [paths, one per cycle]})."""
+        import os
+        by_directory = {}
+        for path in filepath_list:
+            directory, name = os.path.split(os.path.abspath(path))
+            by_directory.setdefault(directory, []).append(name)
+        frame_indexed = {}
+        for index, directory in enumerate(sorted(by_directory)):
+            for name in sorted(by_directory[directory]):
+                frame_indexed.setdefault(index, []).append(os.path.join(directory, name))
+        field_indexed = {}
+        for frame, fields in frame_indexed.items():
+            for f, field in enumerate(fields):
+                field_indexed.setdefault(f, []).append(field)
+        return frame_indexed, field_indexed
+
+    @staticmethod
+    def trace_to_binary(trace):
+        return [spot is not None for spot in trace]                 # flexlibrary.py:1157-1158
+
+    @staticmethod
+    def truefalse_to_onoff(pattern):
+        return ' '.join(['[ON] ' if p else '[OFF]' for p in pattern])   # flexlibrary.py:1161-1162
+
+    @staticmethod
+    def trace_to_photometry(trace, method='mexican_hat', return_invalid=True, **kwargs):
+        """[(h, w, photometry)] of a trace's Spots, (None, None, None) where it has none.  flexlibrary.py:1165-1170.
+        Spot by Spot (one small launch each for the hat); the experiment classes measure whole experiments in one."""
+        return [(spot.h, spot.w, spot.photometry(method=method, return_invalid=return_invalid, **kwargs))
+                if spot is not None else (None, None, None) for spot in trace]
+
+    @staticmethod
     def accumulate_offsets(offsets):
         """Offsets relative to the preceding image -> offsets relative to the first.  flexlibrary.py:567-593."""
         if offsets[0] != (0, 0):
@@ -377,6 +432,212 @@ class Experiment(object):
         return traces, res[1]
 
 
+# ---- sequence experiments: every track of every field and channel through one launch (sequencing.py, include/fsq_sequence.h) ----
+
+def _photometry_plan(method, kwargs):
+    """Spot.photometry's dispatch (flexlibrary.py:286-317) for a whole experiment -> dict(method, device, radius, brim_size,
+    scaling, default).  `device` is the kernel's method: the hat, or the spot_size window ('simple'; it also gives
+    gaussian_volume its positions and validity, the volumes come from the fit tuples on the host)."""
+    kwargs = dict(kwargs or {})
+    override = kwargs.pop('photometry_method', None)
+    if override is not None:
+        method = override
+    plan = dict(method=method, device='simple', radius=None, brim_size=0, scaling=10 ** 6, default=0)
+    if method == 'mexican_hat':
+        plan.update(device='mexican_hat', brim_size=kwargs.pop('brim_size', 6), radius=kwargs.pop('radius', 9))
+    elif method == 'gaussian_volume':
+        plan.update(scaling=kwargs.pop('scaling', 10 ** 6), default=kwargs.pop('default', 0))
+    elif method in ('sextractor', 'maximum', 'sigmas'):
+        raise NotImplementedError("photometry method %r is not built" % (method,))
+    elif method != 'simple':
+        raise ValueError("Uknown method specified.")                   # flexlibrary.py:315
+    if kwargs:
+        raise TypeError("%s photometry got an unexpected keyword argument %r" % (method, sorted(kwargs)[0]))
+    return plan
+
+
+def _sequence_records(experiments, plan, interpolate):
+    """The traces of many SequenceExperiments through sequencing.sequence_photometry_records: one launch per group of
+    sequences with the same number of frames, frame shape and Spot size.  -> one dict per experiment: `hw` [n][F] of (h, w) or
+    None, `values` [n][F] photometry or None, `flags` uint8 [n, F], `valid` bool [n], `size`."""
+    from . import sequencing as _sq
+    groups, out = {}, [None] * len(experiments)
+    for k, ex in enumerate(experiments):
+        F = len(ex.peptide_frames)
+        shape = tuple(ex.peptide_frames[0].image.shape)
+        if any(tuple(fr.image.shape) != shape for fr in ex.peptide_frames):
+            raise ValueError("all frames of a SequenceExperiment must have one shape")
+        traces = ex.spot_traces or []
+        sizes = set(spot.size for trace in traces for spot in trace if spot is not None)
+        if len(sizes) > 1:
+            raise NotImplementedError("Spots of different sizes in one SequenceExperiment")
+        size = sizes.pop() if sizes else 5
+        if any(len(trace) != F for trace in traces):
+            raise ValueError("every trace needs one entry per frame")
+        offsets = ex.offsets if ex.offsets is not None else [(0, 0)] * F
+        if len(offsets) != F:
+            raise ValueError("offsets must have one entry per frame")
+        groups.setdefault((F,) + shape + (size,), []).append((k, ex, traces, offsets))
+    for (F, H, W, size), members in groups.items():
+        hw_in, seq = [], []
+        for s, (k, ex, traces, offsets) in enumerate(members):
+            for trace in traces:
+                hw_in.append([(-1, -1) if spot is None else (spot.h, spot.w) for spot in trace])
+                seq.append(s)
+        n = len(hw_in)
+        off = np.array([[(float(o[0]), float(o[1])) for o in offsets] for _, _, _, offsets in members], dtype=np.float64)
+        radius = plan['radius'] if plan['radius'] is not None else (size - 1) // 2
+        if n:
+            frames = np.stack([np.asarray(fr.image) for _, ex, _, _ in members for fr in ex.peptide_frames])
+            rec = _sq.sequence_photometry_records(frames.reshape((len(members), F) + frames.shape[1:]),
+                                                  np.asarray(hw_in).reshape(n, F, 2), seq, off, method=plan['device'], radius=radius,
+                                                  brim_size=plan['brim_size'], spot_size=size, interpolate=interpolate, counts=False)
+        else:
+            _sq.check_arguments((len(members), F, H, W), np.zeros((0, F, 2), np.int32), [], off, plan['device'], radius,
+                                plan['brim_size'], size)
+        start = 0
+        for s, (k, ex, traces, offsets) in enumerate(members):
+            m = len(traces)
+            if not m:
+                out[k] = dict(hw=[], values=[], flags=np.zeros((0, F), np.uint8), valid=np.zeros(0, bool), size=size)
+                continue
+            sl = slice(start, start + m)
+            start += m
+            flags = rec['flags'][sl]
+            have = (flags & 3) != 0
+            hw = [[(h, w) if ok else None for (h, w), ok in zip(row, okrow)]
+                  for row, okrow in zip(rec['hw'][sl].tolist(), have.tolist())]
+            if plan['method'] == 'mexican_hat':
+                values = [[v if ok else None for v, ok in zip(row, okrow)]
+                          for row, okrow in zip(rec['photometry'][sl].tolist(), have.tolist())]
+            elif plan['method'] == 'simple':
+                values = [[int(v) if ok else None for v, ok in zip(row, okrow)]
+                          for row, okrow in zip(rec['photometry'][sl].tolist(), have.tolist())]
+            else:                                                       # gaussian_volume: from the fit tuples; an interpolated Spot has none
+                values = []
+                for trace, okrow in zip(traces, have.tolist()):
+                    values.append([None if not ok else plan['default'] if (spot is None or spot.gaussian_fit is None) else
+                                   float(plan['scaling']) * spot.gaussian_fit[3] * spot.gaussian_fit[4] * spot.gaussian_fit[5]
+                                   for spot, ok in zip(trace, okrow)])
+            out[k] = dict(hw=hw, values=values, flags=flags, valid=rec['trace_valid'][sl], size=size)
+    return out
+
+
+def _append_interpolated_spots(ex, trace, hw_row, size):
+    """What fill_in_trace leaves behind (flexlibrary.py:1842-2032), given the filled-in positions: for every hole of the trace,
+    interpolate_spots appends a new Spot to frame.spots for every position of the span that lies inside its frame - the
+    bookend frames included, on every call.  Returns the merged trace (the trace's own Spots, new Spots or None in the holes)."""
+    F, r = len(trace), (size - 1) // 2
+    merged = list(trace)
+    f = 0
+    while f < F:
+        if trace[f] is not None:
+            f += 1
+            continue
+        g = f
+        while g < F and trace[g] is None:
+            g += 1
+        for i in range(f - 1 if f > 0 else f, (g if g < F else g - 1) + 1):
+            frame = ex.peptide_frames[i]
+            if trace[i] is None:
+                if hw_row[i] is None:
+                    continue
+                h, w = hw_row[i]
+            else:                                                       # a bookend: copied if it passes the same frame test
+                h, w = trace[i].h, trace[i].w
+                if not (r <= h < frame.image.shape[0] - r and r <= w < frame.image.shape[1] - r):
+                    continue
+            spot = Spot(parent_Image=frame, h=h, w=w, size=size, gaussian_fit=None)
+            frame.spots.append(spot)
+            if trace[i] is None:
+                merged[i] = spot
+        f = g
+    return merged
+
+
+def _trace_existing_spots(experiments):
+    """SequenceExperiment.trace_existing_spots for many experiments: one track_fields call per frame shape."""
+    groups = {}
+    for ex in experiments:
+        key = (len(ex.peptide_frames),) + tuple(ex.peptide_frames[0].image.shape)
+        groups.setdefault(key, []).append(ex)
+    for key, members in groups.items():
+        for ex in members:
+            if ex.offsets is None:
+                raise TypeError("'int' object is not iterable")         # (as greedy_particle_tracking without offsets)
+        res = track_fields([[np.array([(s.h, s.w) for s in image.spots]).reshape(-1, 2) for image in ex.peptide_frames]
+                            for ex in members], [list(ex.offsets) for ex in members], key[1:], 2, 0)
+        for ex, r in zip(members, res):
+            flat = [s for image in ex.peptide_frames for s in image.spots]
+            ex.spot_traces = [[(flat[i] if i >= 0 else None) for i in row] for row in r[0]]
+            ex.num_discarded_spots = r[1]
+
+
+def _discard_invalid_traces(experiments, pparams):
+    """SequenceExperiment.discard_invalid_traces (flexlibrary.py:2034-2063) for many experiments in one launch."""
+    pparams = dict(pparams)
+    plan = _photometry_plan(pparams.pop('method', 'mexican_hat'), pparams)
+    recs = _sequence_records(experiments, plan, True)
+    out = []
+    for ex, rec in zip(experiments, recs):
+        valid_traces, invalid_traces = [], []
+        for t, trace in enumerate(ex.spot_traces or []):
+            filled = _append_interpolated_spots(ex, trace, rec['hw'][t], rec['size'])
+            if rec['valid'][t]:
+                valid_traces.append(trace)
+            else:
+                invalid_traces.append(filled)
+        ex.spot_traces = valid_traces
+        out.append(invalid_traces)
+    return out
+
+
+def _binary_trace_categories_photometry(experiments, method, interpolate, discard_invalid, adjustment_function, kwargs):
+    """SequenceExperiment.binary_trace_categories_photometry (flexlibrary.py:2065-2129) for many experiments in one launch."""
+    if discard_invalid:
+        raise DeprecationWarning("discard_invalid is deprecated. Use discard_invalid_traces() functions")
+    plan = _photometry_plan(method, kwargs)
+    recs = _sequence_records(experiments, plan, bool(interpolate))
+    out = []
+    for ex, rec in zip(experiments, recs):
+        order, rows = {}, {}
+        for t, trace in enumerate(ex.spot_traces or []):                # categories in order of first appearance, then their traces
+            order.setdefault(tuple(Experiment.trace_to_binary(trace)), []).append(t)
+        for category, members in order.items():
+            for t in members:
+                if interpolate:
+                    _append_interpolated_spots(ex, ex.spot_traces[t], rec['hw'][t], rec['size'])
+                p = [(hw[0], hw[1], v) if hw is not None else _NONE3 for hw, v in zip(rec['hw'][t], rec['values'][t])]
+                if adjustment_function is not None:
+                    p = [(h, w, adjustment_function(photometry=ph, frame=frame, adjustments=ex.photometry_adjustments))
+                         for frame, (h, w, ph) in enumerate(p)]
+                rows.setdefault(category, []).append(p)
+        out.append(rows)
+    return out
+
+
+_NONE3 = (None, None, None)         # the placeholder of trace_to_photometry; track_photometries_as_csv tells it by identity
+
+
+def _mdma(experiments, tag, method, kwargs):
+    """SequenceExperiment.multiplicative_delta_median_adjustments (flexlibrary.py:2131-2200) for many experiments."""
+    btcps = _binary_trace_categories_photometry(experiments, method, False, False, None, kwargs)
+    out = []
+    for ex, btcp in zip(experiments, btcps):
+        F = len(ex.peptide_frames)
+        all_on = [p for p in btcp.get(tuple([True] * F), []) if all(ph is not None for h, w, ph in p)]
+        ratios = [[] for _ in range(F)]
+        for p in all_on:
+            m = np.median([ph for h, w, ph in p])
+            for i, (h, w, ph) in enumerate(p):
+                ratios[i].append(float(ph - m) / m)
+        if ex.photometry_adjustments is None:
+            ex.photometry_adjustments = {}
+        ex.photometry_adjustments['mdma'] = tuple(np.median(r) if len(r) > 0 else 0.0 for r in ratios)   # (`tag` is not used, :2198)
+        out.append(ex.photometry_adjustments['mdma'])
+    return out
+
+
 class SequenceExperiment(Experiment):
     """A sequence of frames of one field: the reference's SequenceExperiment as far as registration and tracking go
     (flexlibrary.py:1680-1810): `peptide_frames` / `alignment_frames` (Images), `offsets`, `spot_traces`."""
@@ -406,6 +667,424 @@ class SequenceExperiment(Experiment):
             frame_spots=[image.spots for image in self.peptide_frames], frame_shape=self.peptide_frames[0].image.shape,
             offsets=self.offsets, spot_radius=0)
         return self.spot_traces
+
+    def binary_trace_categories(self):
+        """{ON/OFF pattern: [traces]} of self.spot_traces, patterns in order of first appearance.  flexlibrary.py:1812-1840."""
+        categories = {}
+        for trace in self.spot_traces:
+            categories.setdefault(tuple(Experiment.trace_to_binary(trace)), []).append(trace)
+        return categories
+
+    def interpolate_spots(self, start, stop):
+        """New Spots along the line between (start_spot, start_frame) and (stop_spot, stop_frame); one of the two Spots may be
+        None, then the other's position is used throughout.  flexlibrary.py:1842-1974 (host arithmetic: a few operations per
+        frame; whole experiments go through fsq_sequence_photometry).  Every Spot made is appended to its frame's spots; a
+        position outside its frame gives None."""
+        (start_spot, start_frame), (stop_spot, stop_frame) = start, stop
+        if not start_frame < stop_frame:
+            raise ValueError("start_frame must come before stop_frame")
+        if start_spot is not None and stop_spot is not None and not start_frame + 1 < stop_frame:
+            raise ValueError("If neither start_spot or stop_spot are None, stop_frame must have at least one frame between it "
+                             "and start_frame.")
+        if start_spot is None and stop_spot is None:
+            raise ValueError("Both start_spot and stop_spot are None.")
+        offsets = self.offsets if self.offsets is not None else [(0, 0) for _ in self.peptide_frames]
+        if stop_spot is not None:
+            stop_h, stop_w = Experiment.offset_frame_coordinates(offsets=offsets, coordinate=(stop_spot.h, stop_spot.w),
+                                                                 f=start_frame, g=stop_frame)
+        if start_spot is not None:
+            start_h, start_w = start_spot.h, start_spot.w
+        else:
+            start_h, start_w = stop_h, stop_w
+        if stop_spot is None:
+            stop_h, stop_w = start_h, start_w
+        if start_spot is not None and stop_spot is not None and start_spot.size != stop_spot.size:
+            raise ValueError("start_spot.size != stop_spot.size")
+        size = start_spot.size if start_spot is not None else stop_spot.size
+        n, r = stop_frame - start_frame, (size - 1) // 2
+        inc_h, inc_w = float(stop_h - start_h) / n, float(stop_w - start_w) / n
+        assert abs(start_h + inc_h * n - stop_h) < 0.01 and abs(start_w + inc_w * n - stop_w) < 0.01
+        spots = []
+        for i in range(n + 1):
+            frame = self.peptide_frames[start_frame + i]
+            h, w = Experiment.apply_offset((start_h + inc_h * i, start_w + inc_w * i),
+                                           Experiment.get_cumulative_offset(offsets=offsets, f=i + start_frame, g=start_frame))
+            h, w = Experiment.round_coordinates(h, w)
+            if r <= h < frame.image.shape[0] - r and r <= w < frame.image.shape[1] - r:
+                spot = Spot(parent_Image=frame, h=h, w=w, size=size, gaussian_fit=None)
+                frame.spots.append(spot)
+            else:
+                spot = None
+            spots.append(spot)
+        return spots
+
+    def fill_in_trace(self, trace):
+        """The trace with its None entries replaced by interpolated Spots (None where the position leaves the frame).
+        flexlibrary.py:1976-2032; the positions come from fsq_sequence_photometry (one trace, one launch)."""
+        kept, self.spot_traces = self.spot_traces, [trace]
+        try:
+            rec = _sequence_records([self], _photometry_plan('simple', {}), True)[0]
+        finally:
+            self.spot_traces = kept
+        return _append_interpolated_spots(self, trace, rec['hw'][0], rec['size'])
+
+    def discard_invalid_traces(self, **pparams):
+        """Removes from self.spot_traces every trace that, filled in, has a Spot outside its frame or a photometry window
+        that leaves it; returns the removed traces, filled in.  flexlibrary.py:2034-2063."""
+        return _discard_invalid_traces([self], pparams)[0]
+
+    def binary_trace_categories_photometry(self, method='mexican_hat', interpolate=False, discard_invalid=False,
+                                           adjustment_function=None, **kwargs):
+        """binary_trace_categories with every trace replaced by its [(h, w, photometry)] per frame; (None, None, None) where
+        it has no Spot (interpolate=True: only where the filled-in position leaves the frame).  flexlibrary.py:2065-2129."""
+        return _binary_trace_categories_photometry([self], method, interpolate, discard_invalid, adjustment_function, kwargs)[0]
+
+    def multiplicative_delta_median_adjustments(self, tag='mdma', method='mexican_hat', **kwargs):
+        """Per-frame medians of (photometry - median) / median over the traces that are ON in every frame, stored in
+        self.photometry_adjustments['mdma'] and returned; zeros without such traces.  flexlibrary.py:2131-2200."""
+        return _mdma([self], tag, method, kwargs)[0]
+
+    @staticmethod
+    def mdma_adjustment(photometry, frame, adjustments):
+        """photometry * (1 - adjustments['mdma'][frame]).  flexlibrary.py:2202-2221."""
+        if 'mdma' in adjustments:
+            return photometry * (1.0 - adjustments['mdma'][frame])
+        return photometry
+
+    def count_remainders(self):
+        """Number of traces that are ON in every frame.  flexlibrary.py:2223-2231."""
+        return len(self.binary_trace_categories().get(tuple([True] * len(self.peptide_frames)), []))
+
+    def spot_count(self):
+        return sum(len(frame.spots) for frame in self.peptide_frames)             # flexlibrary.py:2285-2293
+
+    def singleton_count(self):
+        return sum(1 for trace in self.spot_traces if len([t for t in trace if t is not None]) == 1)    # :2295-2301
+
+
+def _frame_counts_agree(channels):
+    """The constructors' test (flexlibrary.py:2495-2503, 2652-2663): one number of peptide_frames and of alignment_frames over
+    all channels.  (alignment_frames None counts as the reference's list of None placeholders, one per peptide frame.)"""
+    n_peptide = set(len(chan.peptide_frames) for chan in channels)
+    n_alignment = set(len(chan.alignment_frames if chan.alignment_frames is not None else chan.peptide_frames)
+                      for chan in channels)
+    return len(n_peptide) == len(n_alignment) and len(n_alignment) == 1
+
+
+def _filtered_counts(counts, include_first_frame_only):
+    """Patterns with a single ON -> OFF transition (flexlibrary.py:2935-2946): all ON frames come first."""
+    return {bt: count for bt, count in counts.items()
+            if tuple(sorted(bt, reverse=True)) == bt and (include_first_frame_only or bt[1])}
+
+
+class MultifieldSequenceExperiment(Experiment):
+    """SequenceExperiments over several fields (flexlibrary.py:2384-2468).  As in the reference, the class only serves as
+    the base of MultifieldMultichannelSequenceExperiment: its own constructor raises DeprecationWarning."""
+
+    def __init__(self, experimental_fields):
+        self.experimental_fields = experimental_fields
+        raise DeprecationWarning("This class is no longer maintained. Use MultifieldMultichannelSequenceExperiment instead.")
+
+
+class MultichannelSequenceExperiment(SequenceExperiment):
+    """One field of view in several colour channels: `channels` {name: SequenceExperiment}.  flexlibrary.py:2471-2629.
+    Every method that measures gathers all channels into one launch."""
+
+    def __init__(self, channels):
+        if not _frame_counts_agree(list(channels.values())):
+            raise AttributeError("Number of peptide_frames and alignment_framesdoes not match across channels.")
+        self.channels = channels
+
+    def _experiments(self):
+        return list(self.channels.values())
+
+    def _per_channel(self, results):
+        return dict(zip(self.channels.keys(), results))
+
+    def trace_existing_spots(self):
+        _trace_existing_spots(self._experiments())
+
+    def binary_trace_categories(self):
+        return {c: chan.binary_trace_categories() for c, chan in self.channels.items()}
+
+    def binary_trace_categories_photometry(self, method='mexican_hat', interpolate=False, discard_invalid=False,
+                                           adjustment_function=None, **kwargs):
+        return self._per_channel(_binary_trace_categories_photometry(self._experiments(), method, interpolate, discard_invalid,
+                                                                     adjustment_function, kwargs))
+
+    def count_binary_trace_categories(self):
+        merged = self.binary_trace_categories()
+        return {c: {k: len(v) for k, v in chan.items()} for c, chan in merged.items()}, merged
+
+    def filtered_binary_trace_category_counts(self):
+        counts, merged = self.count_binary_trace_categories()
+        return {c: _filtered_counts(chan, False) for c, chan in counts.items()}
+
+    def plot_filtered_binary_trace_counts(self, output_filepaths):
+        raise DeprecationWarning("Deprecating for now in favor of outputting CSV files. Assume this function is no longer "
+                                 "maintained.")
+
+    def count_discarded_spots(self):
+        return {c: chan.num_discarded_spots for c, chan in self.channels.items()}
+
+    def spot_count(self):
+        return {c: chan.spot_count() for c, chan in self.channels.items()}
+
+    def trace_count(self):
+        return {c: len(chan.spot_traces) for c, chan in self.channels.items()}
+
+    def singleton_count(self):
+        return {c: chan.singleton_count() for c, chan in self.channels.items()}
+
+    def get_offsets(self):
+        return {c: chan.offsets for c, chan in self.channels.items()}
+
+    def discard_invalid_traces(self, **pparams):
+        return self._per_channel(_discard_invalid_traces(self._experiments(), pparams))
+
+    def multiplicative_delta_median_adjustments(self, tag='mdma', method='mexican_hat', channels=None, **kwargs):
+        names = [c for c in self.channels if channels is None or c in channels]
+        return dict(zip(names, _mdma([self.channels[c] for c in names], tag, method, kwargs)))
+
+    def count_remainders(self):
+        return {c: chan.count_remainders() for c, chan in self.channels.items()}
+
+
+class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
+    """A sequencing experiment: `experimental_fields`, a list of MultichannelSequenceExperiments, and `invalid_fields_mask`
+    (False = the field is left out where ignore_invalid_fields is set).  flexlibrary.py:2632-3263.
+
+    trace_existing_spots, discard_invalid_traces, binary_trace_categories_photometry, track_photometries_as_csv and
+    multiplicative_delta_median_adjustments gather every field and channel and run one tracking call / one
+    fsq_sequence_photometry launch (per frame shape).  Nested results keep the reference's layout
+    {channel: {field: {pattern: ...}}}: channels in the order of the fields' `channels` dicts, fields ascending, patterns in
+    order of first appearance in spot_traces."""
+
+    def __init__(self, experimental_fields, invalid_fields_mask=None):
+        if not _frame_counts_agree([chan for ex in experimental_fields for chan in ex.channels.values()]):
+            raise AttributeError("Number of peptide_frames and alignment_framesdoes not match across fields and channels.")
+        self.experimental_fields = experimental_fields
+        if invalid_fields_mask is not None:
+            if len(invalid_fields_mask) != len(self.experimental_fields):
+                raise AttributeError("invalid_fields_mask must be the same length as experimental_fields.")
+            self.invalid_fields_mask = invalid_fields_mask
+        else:
+            self.invalid_fields_mask = [True] * len(self.experimental_fields)
+
+    def _fields(self, ignore_invalid_fields=False):
+        return [(e, ex) for e, ex in enumerate(self.experimental_fields)
+                if not (ignore_invalid_fields and not self.invalid_fields_mask[e])]
+
+    def _sequences(self, ignore_invalid_fields=False):
+        """[(field index, channel name, SequenceExperiment)] of the fields in use."""
+        return [(e, c, chan) for e, ex in self._fields(ignore_invalid_fields) for c, chan in ex.channels.items()]
+
+    def _per_field(self, sequences, results, ignore_invalid_fields):
+        """Results per sequence -> the reference's list over ALL fields of {channel: result} (False for a field left out)."""
+        out = [False if (ignore_invalid_fields and not self.invalid_fields_mask[e]) else {}
+               for e in range(len(self.experimental_fields))]
+        for (e, c, _), r in zip(sequences, results):
+            out[e][c] = r
+        return out
+
+    @staticmethod
+    def _merge(sequences, results):
+        merged = {}
+        for (e, c, _), categories in zip(sequences, results):
+            per_field = merged.setdefault(c, {}).setdefault(e, {})
+            for k, v in categories.items():
+                per_field.setdefault(k, [])
+                per_field[k] += v
+        return merged
+
+    def trace_existing_spots(self, parallel=False, ignore_invalid_fields=False):
+        if parallel:
+            raise NotImplementedError("Classes in multiple processes do not share state, therefore if we want to parallelize "
+                                      "this function, we will need to shuttle information between instances.")
+        _trace_existing_spots([chan for _, _, chan in self._sequences(ignore_invalid_fields)])
+
+    def binary_trace_categories(self, ignore_invalid_fields=False):
+        seqs = self._sequences(ignore_invalid_fields)
+        return self._merge(seqs, [chan.binary_trace_categories() for _, _, chan in seqs])
+
+    def binary_trace_categories_photometry(self, method='mexican_hat', interpolate=False, discard_invalid=False,
+                                           adjustment_function=None, ignore_invalid_fields=False, **kwargs):
+        seqs = self._sequences(ignore_invalid_fields)
+        return self._merge(seqs, _binary_trace_categories_photometry([chan for _, _, chan in seqs], method, interpolate,
+                                                                     discard_invalid, adjustment_function, kwargs))
+
+    def track_photometries_as_csv(self, filepath, dialect='excel', photometry_method='mexican_hat', save_averages=True,
+                                  discard_invalid=False, ignore_invalid_fields=False, adjustment_function=None, **kwargs):
+        """One row per track: CHANNEL, FIELD, H, W, CATEGORY and either AVERAGE_INTENSITY (numpy.mean over the frames the Spot
+        was detected in) or, with save_averages=False, FRAME 0 .. FRAME n-1 with holes filled in by interpolation ('0' where
+        the filled-in position leaves the frame).  H, W are those of the first frame that has a Spot.  Returns the number of
+        rows.  flexlibrary.py:2755-2892."""
+        import csv
+        if discard_invalid:
+            raise DeprecationWarning("discard_invalid is deprecated. Use discard_invalid_traces() functions")
+        btcp = self.binary_trace_categories_photometry(method=photometry_method, interpolate=not save_averages,
+                                                       discard_invalid=discard_invalid, ignore_invalid_fields=ignore_invalid_fields,
+                                                       adjustment_function=adjustment_function, **kwargs)
+        rows = 0
+        with open(filepath, 'w') as output_file:
+            writer = csv.writer(output_file, dialect=dialect)
+            if save_averages:
+                writer.writerow(['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY', 'AVERAGE_INTENSITY'])
+            else:
+                n_frames = len(list(self.experimental_fields[0].channels.values())[0].peptide_frames)
+                writer.writerow(['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY'] + ['FRAME ' + str(i) for i in range(n_frames)])
+            for chan, categories in btcp.items():
+                for e, ex in categories.items():
+                    for category, trace_photometries in ex.items():
+                        for photometry in trace_photometries:
+                            # (the placeholder is told by identity, as the reference does: an adjustment_function builds new
+                            #  tuples, and then the first frame's entry is taken whatever it holds, flexlibrary.py:2872-2874)
+                            h, w = [fp[:2] for fp in photometry if fp is not _NONE3][0]
+                            if save_averages:
+                                mean = np.mean([fp[2] for fp in photometry if fp[2] is not None])
+                                writer.writerow([str(chan), str(e), str(h), str(w), str(category), str(mean)])
+                            else:
+                                writer.writerow([str(chan), str(e), str(h), str(w), str(category)] +
+                                                [str(fp[2]) if fp[2] is not None else '0' for fp in photometry])
+                            rows += 1
+        return rows
+
+    def count_binary_trace_categories(self, ignore_invalid_fields=False):
+        merged = self.binary_trace_categories(ignore_invalid_fields=ignore_invalid_fields)
+        counts = {c: {e: {k: len(v) for k, v in ex.items()} for e, ex in chan.items()} for c, chan in merged.items()}
+        return counts, merged
+
+    def filtered_binary_trace_category_counts(self, include_first_frame_only=True, ignore_invalid_fields=False):
+        """Counts of the patterns with a single ON -> OFF transition; include_first_frame_only=False leaves out the
+        pattern that is ON in the first frame only.  flexlibrary.py:2911-2946."""
+        counts, merged = self.count_binary_trace_categories(ignore_invalid_fields=ignore_invalid_fields)
+        return {c: {e: _filtered_counts(ex, include_first_frame_only) for e, ex in chan.items()} for c, chan in counts.items()}
+
+    def category_counts_as_csv(self, filepath, filtered=True, collate_fields=False, dialect='excel',
+                               ignore_invalid_fields=False):
+        """Pattern, (Field,) Channel, Count rows of filtered_binary_trace_category_counts; patterns and channels sorted,
+        fields summed unless collate_fields.  Returns filepath.  flexlibrary.py:2948-3024."""
+        import csv
+        if filtered:
+            to_save = self.filtered_binary_trace_category_counts(ignore_invalid_fields=ignore_invalid_fields)
+        else:
+            to_save = self.count_binary_trace_categories(ignore_invalid_fields=ignore_invalid_fields)
+        channels = sorted(to_save.keys())            # (filtered=False: a tuple has no keys - the reference fails the same way)
+        patterns = sorted(set(pattern for fields in to_save.values() for counts in fields.values() for pattern in counts))
+        with open(filepath, 'w') as output_file:
+            writer = csv.writer(output_file, dialect=dialect)
+            writer.writerow(["Pattern", "Field", "Channel", "Count"] if collate_fields else ["Pattern", "Channel", "Count"])
+            for pattern in patterns:
+                onoff = Experiment.truefalse_to_onoff(pattern)
+                for chan in channels:
+                    if collate_fields:
+                        for e, ex in to_save[chan].items():
+                            writer.writerow([onoff, str(e), str(chan), str(ex[pattern]) if pattern in ex else '0'])
+                    else:
+                        writer.writerow([onoff, str(chan), str(sum(ex[pattern] for ex in to_save[chan].values() if pattern in ex))])
+        return filepath
+
+    def category_counts_as_string(self, filtered=True, collate_fields=False, ignore_invalid_fields=False):
+        """The filtered counts as a multi-line string.  flexlibrary.py:3026-3077."""
+        if not filtered:
+            raise NotImplementedError("filtered=False not yet implemented.")
+        to_string = self.filtered_binary_trace_category_counts(ignore_invalid_fields=ignore_invalid_fields)
+        out = ''
+        for chan, ex in sorted(to_string.items(), key=lambda x: x[0]):
+            if collate_fields:
+                for e, patterns in ex.items():
+                    out += " Channel " + str(chan) + " Frame " + str(e) + "\n"
+                    for pattern, count in sorted(patterns.items(), key=lambda x: x[0]):
+                        out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
+            else:
+                merged = {}
+                for patterns in ex.values():
+                    for pattern, count in patterns.items():
+                        merged[pattern] = merged.get(pattern, 0) + count
+                out += str(chan) + "\n"
+                for pattern, count in sorted(merged.items(), key=lambda x: x[0]):
+                    out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
+        return out
+
+    def _summed(self, name, ignore_invalid_fields):
+        count = {}
+        for e, ex in self._fields(ignore_invalid_fields):
+            for c, num in getattr(ex, name)().items():
+                count[c] = count.get(c, 0) + num
+        return count
+
+    def count_discarded_spots(self, ignore_invalid_fields=False):
+        return self._summed('count_discarded_spots', ignore_invalid_fields)
+
+    def spot_count(self, ignore_invalid_fields=False):
+        return self._summed('spot_count', ignore_invalid_fields)
+
+    def trace_count(self, ignore_invalid_fields=False):
+        return self._summed('trace_count', ignore_invalid_fields)
+
+    def singleton_count(self, ignore_invalid_fields=False):
+        return self._summed('singleton_count', ignore_invalid_fields)
+
+    def get_offsets(self, ignore_invalid_fields=False):
+        return {e: ex.get_offsets() for e, ex in self._fields(ignore_invalid_fields)}
+
+    def get_offsets_by_frame(self, ignore_invalid_fields=False):
+        """{frame: {field: {channel: (d_h, d_w)}}}.  flexlibrary.py:3142-3157."""
+        by_frame = {}
+        for e, ex_offsets in self.get_offsets().items():
+            if ignore_invalid_fields and not self.invalid_fields_mask[e]:
+                continue
+            for c, chan_offsets in ex_offsets.items():
+                for f, frame_offset in enumerate(chan_offsets):
+                    by_frame.setdefault(f, {}).setdefault(e, {}).setdefault(c, (frame_offset[0], frame_offset[1]))
+        return by_frame
+
+    def save_offsets_as_dict(self, filename, ignore_invalid_fields=False):
+        import pickle
+        with open(filename, 'wb') as f:
+            pickle.dump(self.get_offsets_by_frame(ignore_invalid_fields=ignore_invalid_fields), f)
+
+    def offsets_as_string(self, ignore_invalid_fields=False):
+        """get_offsets_by_frame as text, with mean and standard deviation per field and per frame.  flexlibrary.py:3168-3201
+        (the labels of the per-frame lines are the reference's)."""
+        out = ''
+        for f, frame_offsets in sorted(self.get_offsets_by_frame(ignore_invalid_fields=ignore_invalid_fields).items()):
+            out += "Frame " + str(f) + "\n"
+            for e, ex_offsets in sorted(frame_offsets.items(), key=lambda x: x[0]):
+                out += "    Field " + str(e) + "\n"
+                for c, (h, w) in sorted(ex_offsets.items(), key=lambda x: x[0]):
+                    out += "        Channel " + str(c) + " " + str((h, w)) + "\n"
+                all_h, all_w = [h for h, w in ex_offsets.values()], [w for h, w in ex_offsets.values()]
+                out += "        Mean Offsets for Field " + str(e) + " = " + str((np.mean(all_h), np.mean(all_w))) + "\n"
+                out += "        Std.Dev. Offsets for Field " + str(e) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
+            all_h = [h for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
+            all_w = [w for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
+            out += "    Mean Offsets for Frame " + str(f) + str((np.mean(all_h), np.mean(all_w))) + "\n"
+            out += "        Std.Dev. Offsets for Field " + str(f) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
+        return out
+
+    def discard_invalid_traces(self, ignore_invalid_fields=False, **pparams):
+        seqs = self._sequences(ignore_invalid_fields)
+        return self._per_field(seqs, _discard_invalid_traces([chan for _, _, chan in seqs], pparams), ignore_invalid_fields)
+
+    def multiplicative_delta_median_adjustments(self, tag='mdma', method='mexican_hat', channels=None,
+                                                ignore_invalid_fields=False, **kwargs):
+        seqs = self._sequences(ignore_invalid_fields)           # (`channels` is not passed on, flexlibrary.py:3215-3218)
+        return self._per_field(seqs, _mdma([chan for _, _, chan in seqs], tag, method, kwargs), ignore_invalid_fields)
+
+    def count_remainders(self, ignore_invalid_fields=False):
+        return [ex.count_remainders() if not (ignore_invalid_fields and not self.invalid_fields_mask[e]) else False
+                for e, ex in enumerate(self.experimental_fields)]
+
+    def remainder_threshold_fields(self, channels=None, min_remainders=5):
+        """Marks the fields that have fewer than min_remainders remainders in one of the channels (all of them, or those
+        named) as invalid; returns self.invalid_fields_mask.  flexlibrary.py:3231-3263."""
+        for e, counts in enumerate(self.count_remainders(ignore_invalid_fields=True)):
+            if counts is False:
+                continue
+            if any(n < min_remainders for c, n in counts.items() if channels is None or c in channels):
+                self.invalid_fields_mask[e] = False
+        return self.invalid_fields_mask
 
 
 from .stepfitting import PhotometryTrace, PlateauTrace  # noqa: E402  (flexlibrary.py:1595-1662; re-exported here)
