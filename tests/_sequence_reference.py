@@ -135,3 +135,22 @@ def category_counts(category, trace_seq, select=None):
     keys = list(groups)
     return {"seq": np.array([k[0] for k in keys], np.int32), "pattern": np.array([k[1] for k in keys], np.uint64),
             "count": np.array([groups[k][0] for k in keys], np.int32), "first": np.array([groups[k][1] for k in keys], np.int32)}
+
+
+def category_counts_unique(category, trace_seq, select=None):
+    """category_counts for millions of traces: the same groups, counts and first (= smallest) indices from one stable sort,
+    in order of first appearance."""
+    cat = np.asarray(category, dtype=np.uint64).reshape(-1)
+    seq = np.asarray(trace_seq).reshape(-1).astype(np.int64)
+    idx = np.arange(len(cat)) if select is None else np.flatnonzero(np.asarray(select).reshape(-1))
+    c, s = cat[idx], seq[idx]
+    o = np.lexsort((c, s))                                          # stable: equal keys stay in index order
+    cs, ss = c[o], s[o]
+    new = np.ones(len(o), bool)
+    new[1:] = (cs[1:] != cs[:-1]) | (ss[1:] != ss[:-1])
+    starts = np.flatnonzero(new)
+    first = idx[o[starts]]
+    count = np.diff(np.append(starts, len(o)))
+    order = np.argsort(first, kind="stable")
+    return {"seq": ss[starts][order].astype(np.int32), "pattern": cs[starts][order].astype(np.uint64),
+            "count": count[order].astype(np.int32), "first": first[order].astype(np.int32)}

@@ -153,7 +153,9 @@ def plateaus_from_steps(steps, n, lum):
     return [(bounds[i], bounds[i + 1] - 1, np.mean(lum[bounds[i]:bounds[i + 1]])) for i in range(len(bounds) - 1)]
 
 
-def t_test_filter(lum, plateaus, p_threshold, drop_sort=True, no_merge_start=0, flags=None):
+def t_test_filter(lum, plateaus, p_threshold, drop_sort=True, no_merge_start=0, flags=None, tie_reverse=False):
+    """tie_reverse=True is NOT the reference's order: equal p are visited last pair first (the order an unstable sort could
+    give).  The limit tests use it to prove that a case with tied p depends on the tie order."""
     flags = flags or Flags()
     lum = np.asarray(lum, dtype=np.float64)
     pl = list(plateaus)
@@ -178,6 +180,8 @@ def t_test_filter(lum, plateaus, p_threshold, drop_sort=True, no_merge_start=0, 
                 flags.unsupported = True
                 return None
             order = cpython_sort_desc(ps) if any(math.isnan(p) for p in ps) else sorted(range(len(ps)), key=ps.__getitem__, reverse=True)
+            if tie_reverse and not any(math.isnan(p) for p in ps):
+                order = sorted(range(len(ps)), key=lambda r: (ps[r], r), reverse=True)
             fin = sorted(p for p in ps if np.isfinite(p))
             if any(_near(fin[i], fin[i + 1]) and fin[i] != fin[i + 1] for i in range(len(fin) - 1)):
                 flags.near = True
@@ -232,7 +236,7 @@ def unmirror_plateaus(plateaus, m):
 
 
 def stepfit(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, photometry_min=None, window_radius=6,
-            drop_sort=True):
+            drop_sort=True, window_lengths=(2, 4, 8, 16), M=10):
     """Returns (photometries, ck_filtered, plateaus, t_filtered_plateaus, flags) for one trace (unmirrored lists)."""
     ph = [0.0 if v is None else float(v) for v in photometries]
     if photometry_min is not None:
@@ -242,7 +246,7 @@ def stepfit(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, pho
     m = mirror_start
     mir = [x for x in reversed(ph[:m])] + list(ph)
     flags = Flags()
-    ck = ck_filter(mir) if chung_kennedy > 0 else mir
+    ck = ck_filter(mir, window_lengths=window_lengths, M=M) if chung_kennedy > 0 else mir
     steps = sliding_steps(ck, window_radius, p_threshold, flags)
     pl = plateaus_from_steps(steps, len(mir), mir)
     tf = t_test_filter(mir, pl, p_threshold, drop_sort=drop_sort, no_merge_start=m, flags=flags)

@@ -283,10 +283,70 @@ def check_conditions(name, out, H, W, radius):
     assert 2 * n["singleton"] <= len(hw), (name, "more than half of the traces are singletons")
 
 
+# ---- tests/golden/sequence_limits.npz: Spot.mexican_hat_photometry_metric around the 16-register window ---------------------
+HAT_SIDE = 44                                # an unclipped radius-15 window (31 x 31) fits around (22, 22)
+HAT_RADII = (12, 13, 14, 15, 16, 17)
+HAT_FIELDS = ("random", "tied", "constant", "two_valued", "top")
+HAT_POSITIONS = ((22, 22), (21, 23), (15, 15), (16, 28), (0, 22), (43, 22), (22, 0), (22, 43), (0, 0), (0, 43), (43, 0), (43, 43))
+
+
+def hat_brims(radius):
+    """0, a middle width, a crown of one pixel, no crown."""
+    return (0, 6, radius, radius + 1)
+
+
+def hat_frame(field, wide, radius):
+    """One 44 x 44 frame (uint16, or uint32 with wide): random; heavily tied; constant; two values split so that the ring
+    around (22, 22) holds as many low as high pixels (its median ends in .5); every pixel at the top of the uint32 range."""
+    rng = np.random.default_rng(5000 + 100 * HAT_FIELDS.index(field) + 10 * int(wide) + radius)
+    top = 2 ** 31 if wide else 65536
+    if field == "random":
+        fr = rng.integers(0, top, (HAT_SIDE, HAT_SIDE), dtype=np.int64)
+    elif field == "tied":
+        fr = rng.integers(0, top, (HAT_SIDE, HAT_SIDE), dtype=np.int64) // (top // 16)
+    elif field == "constant":
+        fr = np.full((HAT_SIDE, HAT_SIDE), int(rng.integers(1, top)), dtype=np.int64)
+    elif field == "two_valued":
+        lo = int(rng.integers(0, top // 2))
+        hi = lo + 1 + 2 * int(rng.integers(0, top // 4))
+        i = np.arange(HAT_SIDE * HAT_SIDE).reshape(HAT_SIDE, HAT_SIDE)
+        fr = np.where(i < 22 * HAT_SIDE + 22, lo, hi).astype(np.int64)
+    else:
+        fr = np.full((HAT_SIDE, HAT_SIDE), top - 1, dtype=np.int64)
+        fr[rng.random((HAT_SIDE, HAT_SIDE)) < 0.3] -= 1
+    return fr.astype(np.uint32 if wide else np.uint16)
+
+
+def gen_limits(fl, out_path):
+    """phot [wide][radius][field][brim][position] float64: the reference's own hat on an int64 copy of every frame."""
+    phot = np.zeros((2, len(HAT_RADII), len(HAT_FIELDS), 4, len(HAT_POSITIONS)))
+    crc = np.zeros((2, len(HAT_RADII), len(HAT_FIELDS)), np.int64)
+    import zlib
+    for wide in (0, 1):
+        for ri, radius in enumerate(HAT_RADII):
+            for fi, field in enumerate(HAT_FIELDS):
+                fr = hat_frame(field, bool(wide), radius)
+                crc[wide, ri, fi] = zlib.crc32(fr.tobytes())
+                im = fl.Image(image=fr.astype(np.int64))
+                for bi, brim in enumerate(hat_brims(radius)):
+                    for pi, (h, w) in enumerate(HAT_POSITIONS):
+                        spot = fl.Spot(im, h, w, 1, gaussian_fit=None)      # (size 1 fits on every border)
+                        phot[wide, ri, fi, bi, pi] = float(spot.mexican_hat_photometry_metric(brim_size=brim, radius=radius))
+                if field == "two_valued":                           # the ring of width 6 around (22, 22): median ends in .5
+                    v = phot[wide, ri, fi, 1, 0]
+                    n_crown = (2 * radius + 1 - 12) ** 2
+                    assert n_crown % 2 == 1 and v != np.floor(v), (wide, radius, v)
+    np.savez_compressed(out_path, phot=phot, frame_crc=crc, radii=np.array(HAT_RADII), positions=np.array(HAT_POSITIONS),
+                        fields=np.array(HAT_FIELDS), side=np.int64(HAT_SIDE))
+    print(out_path, os.path.getsize(out_path), "bytes;", int(np.isnan(phot).sum()), "NaN of", phot.size)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("FSQ_REFERENCE", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "sequence_experiment.npz"))
+    ap.add_argument("--limits", action="store_true",
+                    help="write only tests/golden/sequence_limits.npz (the hat at radii 12 - 17); the other fixture stays")
     a = ap.parse_args()
     os.environ["FSQ_REFERENCE"] = a.reference
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -295,6 +355,8 @@ def main():
     ref = refload.load_reference()
     refload.load("stepfitting_library", "stepfitting_library.py")
     fl = refload.load_flexlibrary(ref).fl
+    if a.limits:
+        return gen_limits(fl, os.path.join(os.path.dirname(a.out), "sequence_limits.npz"))
 
     out = {"channels": np.array(CHANNELS), "spot_size": np.int64(SPOT_SIZE)}
     # (name, seed, fields, frames, H, W, spots per sequence, pixel scale, small hat setting)

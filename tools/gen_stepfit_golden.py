@@ -38,6 +38,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("FSQ_REFERENCE", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "stepfit_traces.npz"))
+    ap.add_argument("--limits", action="store_true",
+                    help="write only tests/golden/stepfit_limits.npz (traces at the 8192-frame limit); the other fixtures stay")
     a = ap.parse_args()
     os.environ["FSQ_REFERENCE"] = a.reference
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -61,6 +63,9 @@ def main():
 
         def photometry(self, method=None, **kw):
             return self.v
+
+    if a.limits:
+        return gen_limits(sf, fl, rec, Stub, os.path.join(os.path.dirname(a.out), "stepfit_limits.npz"))
 
     # (length, kind, mirror, ck, window_radius, drop_sort, thr, special)
     cases = []
@@ -160,6 +165,108 @@ def main():
     np.savez_compressed(a.out, **out)
     print("wrote", a.out, os.path.getsize(a.out), "bytes")
     gen_timetrace(fl, os.path.join(os.path.dirname(a.out), "stepfit_timetrace.npz"))
+
+
+# ---- tests/golden/stepfit_limits.npz: traces whose mirrored length is 8191 / 8192 -------------------------------------
+# (frames, mirror_start, chung_kennedy, drop_sort, p_threshold); window_radius 6.  At 1e-6 chance finds no step in 8192 frames
+# of noise, so the first plateau stays whole; the last case (0.01) starts its t-filter with more than 64 plateau pairs.
+LIMIT_CASES = ((8188, 3, 0, True, 1e-6), (8189, 3, 0, True, 1e-6), (8189, 3, 1, True, 1e-6), (8192, 0, 0, True, 1e-6),
+               (8192, 0, 1, True, 1e-6), (8189, 3, 0, False, 1e-6), (8189, 3, 0, True, 0.01))
+
+
+def limits_trace(seed, n):
+    """One long first plateau (more than 7700 frames) and three of 150 - 170 frames, UNROUNDED: the sum of full-mantissa
+    doubles depends on the order of the additions, so a mean over a plateau pins numpy's pairwise order."""
+    rng = np.random.default_rng(seed)
+    c1 = 7700 + int(rng.integers(0, 8))
+    c2 = c1 + 150 + int(rng.integers(0, 20))
+    c3 = c2 + 150 + int(rng.integers(0, 20))
+    i = np.arange(n)
+    level = 3.0 - (i >= c1) - (i >= c2) - (i >= c3)
+    return level * 40000.0 + 5000.0 + rng.normal(0.0, 1500.0, n)
+
+
+def pairwise_max_leaf(n, depth):
+    """Largest block that numpy's pairwise sum of n elements adds up sequentially when the recursion stops after `depth`
+    splits (numpy itself recurses until a block has at most 128 elements)."""
+    if n <= 128 or depth == 0:
+        return n
+    n2 = n // 2
+    n2 -= n2 % 8
+    return max(pairwise_max_leaf(n2, depth - 1), pairwise_max_leaf(n - n2, depth - 1))
+
+
+def gen_limits(sf, fl, rec, Stub, out_path):
+    recs = {k: [] for k in ("len", "mirror", "ck", "drop_sort", "seed", "first_pass_pairs")}
+    thrs = []
+    flat = {k: [] for k in ("ck_out", "p_pairs")}
+    offs = {k: [0] for k in flat}
+    tabs = {k: [] for k in ("pl_trace", "pl_start", "pl_stop", "pl_h", "tf_trace", "tf_start", "tf_stop", "tf_h")}
+    sums = []
+    for ci, (n, mirror, ck, ds, thr) in enumerate(LIMIT_CASES):
+        seed = 77000 + 100 * ci
+        while True:
+            v = limits_trace(seed, n)
+            phot = [float(x) for x in v]
+            tr = fl.Trace.__new__(fl.Trace)
+            tr.trace = [Stub(x) for x in phot]
+            del rec[:]
+            if ds:
+                res = fl.Trace.stepfit_photometries(tr, 0, 0, mirror_start=mirror, chung_kennedy=ck, p_threshold=thr,
+                                                    photometry_min=None)
+                ck_o, pl_o, tf_o = res[1].trace, res[2].trace, res[3].trace
+            else:
+                mir = sf.mirror_photometries(phot, mirror_size=mirror)
+                ckf = mir
+                for c in range(ck):
+                    ckf = sf.chung_kennedy_filter(luminosities=mir, window_lengths=(2, 4, 8, 16))
+                pl = sf.sliding_t_fitter(luminosity_sequence=ckf, window_radius=6, p_threshold=thr)
+                pl = sf.refit_plateaus(mir, pl)
+                tf = sf.t_test_filter(luminosities=mir, plateaus=pl, p_threshold=thr, drop_sort=ds, no_merge_start=mirror)
+                ck_o = sf.unmirror_photometries(ckf, mirror)
+                pl_o, tf_o = sf.unmirror_plateaus(pl, mirror), sf.unmirror_plateaus(tf, mirror)
+            Lm = n + min(mirror, n)
+            ps = np.array(rec, dtype=np.float64)
+            fin = ps[np.isfinite(ps)]
+            bad = bool(np.any(np.abs(fin - thr) <= REL * np.maximum(np.abs(fin), thr)))
+            pairs = np.sort(fin[Lm:])
+            d = np.diff(pairs)
+            bad |= bool(np.any((d > 0) & (d <= REL * np.abs(pairs[1:]))))
+            bad |= bool(np.isnan(ps[Lm:]).any())                   # (>= 64 pairs with a NaN p: not built on the device)
+            # the conditions on the case: a final plateau of more than 7689 frames whose length a 6-level recursion would
+            # sum differently, at least three of 130 - 7689 frames, and a first t-filter pass of at least 64 pairs
+            lens = [o - s + 1 for s, o, _ in tf_o]
+            if thr < 0.01:
+                bad |= not (max(lens) > 7689 and pairwise_max_leaf(max(lens) + min(mirror, n), 6) > 128)
+                bad |= sum(1 for x in lens if 129 < x <= 7689) < 3
+            else:
+                bad |= len(pl_o) - 1 < 64
+            assert seed % 100 < 20, "no seed meets the conditions of limits case %d" % ci
+            if not bad:
+                break
+            seed += 1
+        recs["len"].append(n); recs["mirror"].append(mirror); recs["ck"].append(ck); recs["drop_sort"].append(int(ds))
+        recs["seed"].append(seed); recs["first_pass_pairs"].append(len(pl_o) - 1); thrs.append(thr)
+        sums.append(float(np.sum(v)))
+        for key, arr in (("ck_out", [float(x) for x in ck_o] if ck else []), ("p_pairs", ps[Lm:])):
+            flat[key].extend(list(arr))
+            offs[key].append(len(flat[key]))
+        for pre, pls in (("pl", pl_o), ("tf", tf_o)):
+            for s, o, h in pls:
+                tabs[pre + "_trace"].append(ci); tabs[pre + "_start"].append(s); tabs[pre + "_stop"].append(o)
+                tabs[pre + "_h"].append(float(h))
+        print("limits case %d: n=%d m=%d ck=%d ds=%d seed=%d -> %d / %d plateaus, %d pair tests" %
+              (ci, n, mirror, ck, ds, seed, len(pl_o), len(tf_o), len(ps) - Lm), flush=True)
+    out = {"case_" + k: np.array(v, dtype=np.int64) for k, v in recs.items()}
+    out["case_phot_sum"] = np.array(sums, dtype=np.float64)        # (guards the seeded generator against drift)
+    out["case_thr"] = np.array(thrs, dtype=np.float64)
+    for k, v in flat.items():
+        out[k] = np.array(v, dtype=np.float64)
+        out[k + "_off"] = np.array(offs[k], dtype=np.int64)
+    for k, v in tabs.items():
+        out[k] = np.array(v, dtype=np.float64 if k.endswith("_h") else np.int64)
+    np.savez_compressed(out_path, **out)
+    print("wrote", out_path, os.path.getsize(out_path), "bytes")
 
 
 def timetrace_stack(seed=17, n_frames=40, shape=(96, 96)):
