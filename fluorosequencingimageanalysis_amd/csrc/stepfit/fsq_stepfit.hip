@@ -13,6 +13,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_stepfit.h"
+#include "fsq_pairwise.h"
 
 namespace {
 
@@ -30,48 +31,6 @@ __device__ __forceinline__ bool trace_valid(const Cfg& c, int n)
     if (n < 1 || n > c.max_frames) return false;
     const int Lm = mirrored_len(c, n);
     return Lm <= FSQ_STEPFIT_MAX_MIRRORED && !(c.ck && Lm <= 2);
-}
-
-// ---- numpy pairwise sum of g(i), i in [off, off + n) ----------------------------------------------------------
-template <class G>
-__device__ __forceinline__ double pw_leaf(const G& g, int off, int n)
-{
-    if (n < 8) {
-        double res = 0.;
-        for (int i = 0; i < n; i++) res += g(off + i);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = g(off + k);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-#pragma unroll
-        for (int k = 0; k < 8; k++) r[k] += g(off + i + k);
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += g(off + i);
-    return res;
-}
-// n <= 8192: every split leaves at most n / 2 + 8, so 7 levels reach the 128-element leaves
-template <int D, class G>
-__device__ double pw_sum(const G& g, int off, int n)
-{
-    if constexpr (D == 0) {
-        return pw_leaf(g, off, n);
-    } else {
-        if (n <= 128) return pw_leaf(g, off, n);
-        int n2 = n / 2;
-        n2 -= n2 % 8;
-        return pw_sum<D - 1>(g, off, n2) + pw_sum<D - 1>(g, off + n2, n - n2);
-    }
-}
-__device__ __forceinline__ double np_mean_short(const double* a, int n)      // n <= 128
-{
-    return pw_leaf([a](int i) { return a[i]; }, 0, n) / (double)n;
-}
-__device__ double np_mean(const double* a, int n)
-{
-    return pw_sum<8>([a](int i) { return a[i]; }, 0, n) / (double)n;
 }
 
 // ---- pow(x, -2.0): glibc 2.35 pow (e_pow.c, FMA variant) for y = -2, x > 0 finite (the CK b_diff / f_diff) ------

@@ -3,7 +3,10 @@ Trace.stepfit_photometries (flexlibrary.py:1380-1462) through stepfitting_librar
 
 stepfit_records is the fast path (flat arrays, no Python object per plateau); stepfit_photometries returns the reference's
 4-tuple per trace.  sliding_t_fitter, chung_kennedy_filter, t_test_filter, refit_plateaus and the mirror helpers are
-drop-ins with the reference's names and defaults."""
+drop-ins with the reference's names and defaults.
+
+chi_squared_step_fitter, filter_upsteps, filter_small_steps and stepfit_r_squared (include/fsq_chisq.h) are drop-ins as well;
+chisq_records / chisq_device fit many traces in one launch."""
 import ctypes
 
 import numpy as np
@@ -303,3 +306,210 @@ def unmirror_plateaus(plateaus, mirror_size):
             continue
         out.append((max(a, 0), o, h))
     return out
+
+
+# ---- chi-squared step fitter, plateau merge filters, R^2 (include/fsq_chisq.h) --------------------------------------------
+def _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits):
+    """FsqChisqParams after the reference's own argument check (:433-435)."""
+    from . import _native_chisq as NC
+    if not 0 < num_steps_multiplier <= 1:
+        raise ValueError("num_steps_multiplier has an invalid value of " + str(num_steps_multiplier))
+    if num_steps is not None and not 0 < num_steps:
+        raise ValueError("num_steps has an invalid value of " + str(num_steps))
+    prm = NC.FsqChisqParams()
+    prm.num_steps = 0 if num_steps is None else int(num_steps)
+    prm.min_step_length = max(int(min_step_length), 0)
+    prm.ignore_counterfits = 1 if ignore_counterfits else 0
+    prm.num_steps_multiplier = float(num_steps_multiplier)
+    prm.min_step_magnitude = float(min_step_magnitude)
+    return prm
+
+
+def chisq_device(d_lum, d_len, num_steps_multiplier=1, num_steps=None, min_step_length=2, min_step_magnitude=0.0,
+                 ignore_counterfits=False, fit_cap=0):
+    """fsq_chisq_step_fit on device tensors (float64 [n, max_frames], int32 [n]); returns a dict of device tensors:
+    start, stop, height [n, max_frames], count, n_fits, status [n] and, when fit_cap > 0, best_res, counter_res, S
+    (float64 [n, fit_cap]) and counter_n (int32).  Enqueued on the current stream, not synchronised.  Lengths are not
+    checked here: a trace the device refuses comes back with a status other than 0 and its rows as allocated (zeros)."""
+    from . import _native_chisq as NC
+    torch = _engine._torch()
+    prm = _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits)
+    dev = d_lum.device
+    n, max_frames = int(d_lum.shape[0]), int(d_lum.shape[1])
+    L = NC.lib()
+    ws_bytes = L.fsq_chisq_workspace_bytes(n, max_frames)
+    if ws_bytes < 0:
+        raise ValueError("fsq_chisq_workspace_bytes: invalid shape")
+    out = {"start": torch.zeros((n, max_frames), dtype=torch.int32, device=dev),
+           "stop": torch.zeros((n, max_frames), dtype=torch.int32, device=dev),
+           "height": torch.zeros((n, max_frames), dtype=torch.float64, device=dev),
+           "count": torch.zeros(n, dtype=torch.int32, device=dev), "n_fits": torch.zeros(n, dtype=torch.int32, device=dev),
+           "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    if fit_cap > 0:
+        for k in ("best_res", "counter_res", "S"):
+            out[k] = torch.zeros((n, fit_cap), dtype=torch.float64, device=dev)
+        out["counter_n"] = torch.zeros((n, fit_cap), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+    opt = [out[k].data_ptr() for k in ("best_res", "counter_res", "counter_n", "S")] if fit_cap > 0 else [None] * 4
+    rc = L.fsq_chisq_step_fit(d_lum.data_ptr(), d_len.data_ptr(), n, max_frames, ctypes.byref(prm), out["start"].data_ptr(),
+                              out["stop"].data_ptr(), out["height"].data_ptr(), out["count"].data_ptr(),
+                              out["n_fits"].data_ptr(), opt[0], opt[1], opt[2], opt[3], int(fit_cap), out["status"].data_ptr(),
+                              ws.data_ptr(), int(ws_bytes), torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_chisq_step_fit")
+    out["_ws"] = ws                   # (kept alive until the caller has read the outputs)
+    return out
+
+
+def _lum_rows(sequences):
+    """Luminosity sequences -> (float64 [n, max_frames] host rows, int32 lengths); a NaN has no pinnable reference result."""
+    if isinstance(sequences, np.ndarray) and sequences.ndim == 2:
+        seqs = [np.asarray(r, dtype=np.float64) for r in sequences]
+    else:
+        seqs = [np.array([float(v) for v in s], dtype=np.float64) for s in sequences]
+    lens = np.array([len(s) for s in seqs], dtype=np.int32)
+    rows = np.zeros((len(seqs), max(int(lens.max()) if len(seqs) else 1, 1)), dtype=np.float64)
+    for i, s in enumerate(seqs):
+        if np.isnan(s).any():
+            raise ValueError("trace %d holds a NaN luminosity" % i)
+        rows[i, :len(s)] = s
+    return rows, lens
+
+
+def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step_length=2, min_step_magnitude=0.0,
+                  ignore_counterfits=False, fit_cap=0, device=None):
+    """chi_squared_step_fitter for many traces in one launch, as arrays.
+
+    Returns a dict: "trace", "start", "stop", "height" (one entry per plateau, in trace order), "counts" and "n_fits" per
+    trace, "lengths" and, when fit_cap > 0, "best_res", "counter_res", "S", "counter_n" ([n, fit_cap], row t valid up to
+    n_fits[t]).  Raises the reference's errors for the first trace that has one."""
+    from . import _native_chisq as NC
+    rows, lens = _lum_rows(photometries)
+    _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits)
+    if len(lens) and lens.max() > NC.MAX_FRAMES:
+        raise ValueError("chi_squared_step_fitter: traces are limited to %d frames" % NC.MAX_FRAMES)
+    for n in lens.tolist():
+        if num_steps is not None and not 0 < num_steps < n:
+            raise ValueError("num_steps has an invalid value of " + str(num_steps) + " vs len(luminosity_sequence) = " + str(n))
+        if num_steps is None and n < 2:
+            raise IndexError("list index out of range")            # (the reference sorts an empty list of fits, :502)
+    if len(lens) == 0:
+        return {"trace": np.zeros(0, np.int64), "start": np.zeros(0, np.int32), "stop": np.zeros(0, np.int32),
+                "height": np.zeros(0), "counts": np.zeros(0, np.int64), "n_fits": np.zeros(0, np.int32), "lengths": lens}
+    torch = _engine._torch()
+    dev = torch.device(device or "cuda")
+    out = chisq_device(torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev), num_steps_multiplier, num_steps,
+                       min_step_length, min_step_magnitude, ignore_counterfits, fit_cap)
+    host = {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+    st = host["status"]
+    if (st == NS.STATUS_UNSUPPORTED).any():
+        i = int(np.flatnonzero(st == NS.STATUS_UNSUPPORTED)[0])
+        raise ValueError("num_plateaus = " + str(int(lens[i]) + 1) + " is greater than len(luminosities) = " + str(int(lens[i])))
+    if (st != NS.STATUS_OK).any():
+        raise ValueError("trace %d: invalid length or num_steps" % int(np.flatnonzero(st != NS.STATUS_OK)[0]))
+    cnt = host["count"].astype(np.int64)
+    mask = np.arange(rows.shape[1])[None, :] < cnt[:, None]
+    res = {"trace": np.nonzero(mask)[0].astype(np.int64), "start": host["start"][mask], "stop": host["stop"][mask],
+           "height": host["height"][mask], "counts": cnt, "n_fits": host["n_fits"], "lengths": lens}
+    for k in ("best_res", "counter_res", "S", "counter_n"):
+        if k in host:
+            res[k] = host[k]
+    return res
+
+
+def chi_squared_step_fitter(luminosity_sequence, num_steps_multiplier=1, num_steps=None, min_step_length=2,
+                            min_step_magnitude=0.0, ignore_counterfits=False):
+    """stepfitting_library.chi_squared_step_fitter (:342-505) on the GPU: a list of (start, stop, height) plateaus."""
+    r = chisq_records([luminosity_sequence], num_steps_multiplier, num_steps, min_step_length, min_step_magnitude,
+                      ignore_counterfits)
+    return [(int(s), int(o), np.float64(h)) for s, o, h in zip(r["start"], r["stop"], r["height"])]
+
+
+def _plateau_rows(luminosities, plateaus, what):
+    lum = np.array([float(v) for v in luminosities], dtype=np.float64)
+    if np.isnan(lum).any():
+        raise ValueError(what + ": a NaN luminosity")
+    pls = [(int(a), int(o), float(h)) for a, o, h in plateaus]
+    n = len(lum)
+    if n > NS.MAX_MIRRORED:
+        raise ValueError(what + ": at most %d luminosities" % NS.MAX_MIRRORED)
+    if not (len(pls) >= 1 and 0 <= pls[0][0] and pls[-1][1] < n and all(a <= o for a, o, _ in pls) and
+            all(pls[i][1] + 1 == pls[i + 1][0] for i in range(len(pls) - 1))):
+        raise ValueError("Merged plateaus must be consecutive and lie within the luminosities")
+    st = np.zeros((1, n), np.int32); so = np.zeros((1, n), np.int32); hh = np.zeros((1, n))
+    st[0, :len(pls)] = [a for a, _, _ in pls]; so[0, :len(pls)] = [o for _, o, _ in pls]; hh[0, :len(pls)] = [h for _, _, h in pls]
+    torch = _engine._torch()
+    dev = torch.device("cuda")
+    d = {k: torch.from_numpy(v).to(dev) for k, v in (("lum", lum[None]), ("len", np.array([n], np.int32)), ("s", st), ("o", so),
+                                                       ("h", hh), ("n", np.array([len(pls)], np.int32)))}
+    return d, n, dev, torch
+
+
+def merge_filter_device(d_lum, d_len, d_start, d_stop, d_h, d_n, mode, min_magnitude=None, min_noise_ratio=None):
+    """fsq_stepfit_merge_filter on device tensors (rows of [n, max_frames]); mode 0 filter_upsteps, 1 filter_small_steps.
+    Returns {"start", "stop", "height", "count", "status"} device tensors; enqueued on the current stream."""
+    from . import _native_chisq as NC
+    torch = _engine._torch()
+    dev = d_lum.device
+    n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
+    out = {"start": torch.zeros((n, mf), dtype=torch.int32, device=dev), "stop": torch.zeros((n, mf), dtype=torch.int32, device=dev),
+           "height": torch.zeros((n, mf), dtype=torch.float64, device=dev), "count": torch.zeros(n, dtype=torch.int32, device=dev),
+           "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    rc = NC.lib().fsq_stepfit_merge_filter(d_lum.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
+                                           d_h.data_ptr(), d_n.data_ptr(), int(mode), 0 if min_magnitude is None else 1,
+                                           0.0 if min_magnitude is None else float(min_magnitude),
+                                           0 if min_noise_ratio is None else 1,
+                                           0.0 if min_noise_ratio is None else float(min_noise_ratio), out["start"].data_ptr(),
+                                           out["stop"].data_ptr(), out["height"].data_ptr(), out["count"].data_ptr(),
+                                           out["status"].data_ptr(), None, 0, torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_stepfit_merge_filter")
+    return out
+
+
+def r_squared_device(d_lum, d_len, d_start, d_stop, d_h, d_n):
+    """fsq_stepfit_r_squared on device tensors; returns {"r2", "status"} device tensors."""
+    from . import _native_chisq as NC
+    torch = _engine._torch()
+    dev = d_lum.device
+    n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
+    out = {"r2": torch.zeros(n, dtype=torch.float64, device=dev), "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    rc = NC.lib().fsq_stepfit_r_squared(d_lum.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
+                                        d_h.data_ptr(), d_n.data_ptr(), out["r2"].data_ptr(), out["status"].data_ptr(), None, 0,
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_stepfit_r_squared")
+    return out
+
+
+def _merge_filter(luminosities, plateaus, mode, min_magnitude, min_noise_ratio, what):
+    if len(plateaus) < 2:
+        return list(plateaus)
+    d, n, dev, torch = _plateau_rows(luminosities, plateaus, what)
+    out = merge_filter_device(d["lum"], d["len"], d["s"], d["o"], d["h"], d["n"], mode, min_magnitude, min_noise_ratio)
+    h = {k: v.cpu().numpy() for k, v in out.items()}
+    if h["status"][0] != NS.STATUS_OK:
+        raise ValueError(what + ": invalid plateaus")
+    k = int(h["count"][0])
+    return [(int(h["start"][0, i]), int(h["stop"][0, i]), np.float64(h["height"][0, i])) for i in range(k)]
+
+
+def filter_upsteps(luminosities, plateaus):
+    """stepfitting_library.filter_upsteps (:773-799) on the GPU: merges plateaus until no upstep remains."""
+    return _merge_filter(luminosities, plateaus, 0, None, None, "filter_upsteps")
+
+
+def filter_small_steps(luminosities, plateaus, min_magnitude=None, min_noise_ratio=None):
+    """stepfitting_library.filter_small_steps (:881-926) on the GPU: merges steps below min_magnitude, or below
+    min_noise_ratio * max(sqrt(residuals)) of their two plateaus; a criterion that is None is not applied."""
+    if min_magnitude is not None and min_magnitude < 0:
+        raise ValueError("min_step_magnitude < 0 makes no sense. min_magnitude = " + str(min_magnitude))
+    if min_noise_ratio is not None and min_noise_ratio < 0:
+        raise ValueError("min_step_noise_ratio < 0 makes no sense. min_noise_ratio = " + str(min_noise_ratio))
+    return _merge_filter(luminosities, plateaus, 1, min_magnitude, min_noise_ratio, "filter_small_steps")
+
+
+def stepfit_r_squared(luminosities, plateaus):
+    """stepfitting_library.stepfit_r_squared (:1483-1503) on the GPU: 1 - SS_res / SS_tot over the frames the plateaus span."""
+    d, n, dev, torch = _plateau_rows(luminosities, plateaus, "stepfit_r_squared")
+    out = r_squared_device(d["lum"], d["len"], d["s"], d["o"], d["h"], d["n"])
+    if int(out["status"].cpu()[0]) != NS.STATUS_OK:
+        raise ValueError("stepfit_r_squared: invalid plateaus")
+    return np.float64(out["r2"].cpu().numpy()[0])
