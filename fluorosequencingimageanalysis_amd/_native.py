@@ -127,6 +127,23 @@ def lib():
     return _lib
 
 
+def bind(sigs):
+    """A lib() for a sibling binding module: the handle of lib() with `sigs` (name -> (restype, argtypes)) bound on it, once per
+    handle."""
+    bound = []
+
+    def bound_lib():
+        L = lib()
+        if not (bound and bound[0] is L):
+            for name, (res, args) in sigs.items():
+                f = getattr(L, name)
+                f.restype = res
+                f.argtypes = args
+            bound[:] = [L]
+        return L
+    return bound_lib
+
+
 def source_sha16():
     """Hash of the library's sources (csrc/*.hip, csrc/*.h, include/fsq.h): what profiles/fit_counters_latest.json records so
     that counters taken on one version of the kernels are not reported for another (bench.py)."""

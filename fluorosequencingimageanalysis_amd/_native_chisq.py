@@ -27,17 +27,4 @@ _SIGS = {
 }
 EXPORTED = tuple(_SIGS)
 
-_bound = None
-
-
-def lib():
-    """The library handle of _native.lib() with the chi-squared entries bound."""
-    global _bound
-    L = N.lib()
-    if _bound is not L:
-        for name, (res, args) in _SIGS.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _bound = L
-    return L
+lib = N.bind(_SIGS)                 # the library handle of _native.lib() with the chi-squared entries bound

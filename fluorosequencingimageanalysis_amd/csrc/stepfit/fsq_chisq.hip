@@ -13,6 +13,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_chisq.h"
+#include "fsq_glibc_pow.h"
 #include "fsq_pairwise.h"
 
 namespace {
@@ -22,107 +23,8 @@ constexpr int CS_UNKNOWN = -2, CS_NONE = -1;
 constexpr int MAX_BLOCKS = 8192;
 constexpr int LDS_BYTES_PER_FRAME = 4 * 8 + 7 * 2 + 1, WS_BYTES_PER_FRAME = 5 * 8 + 4;
 
-// pow(x, 2.0) as glibc 2.35 computes it (e_pow.c, FMA variant): fsq_devmath.h's fsq_pow2 and its exp core, inlined here so that the kernels
-// make no call (a call costs a scratch frame).  Negative bases drop their sign (y is even), 0 / inf / nan give x * x, tiny
-// results go through exp's specialcase.
-__device__ __forceinline__ double cs_exp_special(double tmp, unsigned long long sbits, unsigned long long ki)
-{
-    double scale, y;
-    if ((ki & 0x80000000ull) == 0) {
-        sbits -= 1009ull << 52;
-        scale = fsq_dbl(sbits);
-        return 0x1p1009 * fsq_fma(scale, tmp, scale);
-    }
-    sbits += 1022ull << 52;
-    scale = fsq_dbl(sbits);
-    y = scale + scale * tmp;
-    if (y < 1.0) {
-        double hi, lo;
-        lo = scale - y + scale * tmp;
-        hi = 1.0 + y;
-        lo = 1.0 - hi + y + lo;
-        y = (hi + lo) - 1.0;
-        if (y == 0.0) y = 0.0;
-    }
-    return 0x1p-1022 * y;
-}
-
-// exp(x + xtail) of pow: fsq_exp_core<true>
-__device__ __forceinline__ double cs_exp_pow(double x, double xtail)
-{
-    unsigned abstop = (unsigned)(fsq_bits(x) >> 52) & 0x7ff;
-    if (__builtin_expect(abstop - 0x3c9u >= 0x3fu, 0)) {
-        if (abstop - 0x3c9u >= 0x80000000u) return 1.0 + x;
-        if (abstop >= 0x409u) {
-            return (fsq_bits(x) >> 63) ? 0.0 : __builtin_inf();   // __math_uflow / __math_oflow values
-        }
-        abstop = 0;
-    }
-    double kd = fsq_fma(x, EXP_INVLN2N, EXP_SHIFT);
-    unsigned long long ki = fsq_bits(kd);
-    kd -= EXP_SHIFT;
-    double r = fsq_fma(kd, EXP_NEGLN2HIN, x);
-    r = fsq_fma(kd, EXP_NEGLN2LON, r);
-    r = xtail + r;
-    unsigned idx = 2u * ((unsigned)ki & 127u);
-    unsigned long long top = ki << 45;
-    double tail = fsq_dbl(FSQ_EXP_TAB[idx]);
-    unsigned long long sbits = FSQ_EXP_TAB[idx + 1] + top;
-    double r2 = r * r;
-    double p23 = fsq_fma(EXP_C3, r, EXP_C2);
-    double p45 = fsq_fma(r, EXP_C5, EXP_C4);
-    double t = r + tail;
-    double tmp = fsq_fma(p23, r2, t);
-    tmp = fsq_fma(r2 * r2, p45, tmp);
-    if (__builtin_expect(abstop == 0, 0)) return cs_exp_special(tmp, sbits, ki);
-    double scale = fsq_dbl(sbits);
-    return fsq_fma(scale, tmp, scale);
-}
-
-__device__ __forceinline__ double cs_pow2(double x)
-{
-    unsigned long long ix = fsq_bits(x);
-    unsigned topx = (unsigned)(ix >> 52);
-    if (topx - 1u >= 0x7ffu - 1u) {
-        if (2 * ix - 1 >= 2 * 0x7ff0000000000000ull - 1) return x * x;   // 0, inf, nan
-        ix &= 0x7fffffffffffffffull;                                     // y = 2: even, sign dropped
-        topx &= 0x7ff;
-        if (topx == 0) {
-            ix = fsq_bits(fsq_dbl(ix) * 0x1p52);
-            ix &= 0x7fffffffffffffffull;
-            ix -= 52ull << 52;
-        }
-    }
-    unsigned long long tmp = ix - 0x3fe6955500000000ull;
-    int i = (int)((tmp >> 45) & 127);
-    int k = (int)((long long)tmp >> 52);
-    unsigned long long iz = ix - (tmp & (0xfffull << 52));
-    double z = fsq_dbl(iz), kd = (double)k;
-    double invc = FSQ_POW_LOG_TAB[i][0], logc = FSQ_POW_LOG_TAB[i][1], logctail = FSQ_POW_LOG_TAB[i][2];
-    double r = fsq_fma(z, invc, -1.0);
-    double t1 = fsq_fma(kd, POW_LN2HI, logc);
-    double t2 = t1 + r;
-    double lo1 = fsq_fma(kd, POW_LN2LO, logctail);
-    double lo2 = t1 - t2 + r;
-    double ar = POW_A[0] * r;
-    double ar2 = r * ar;
-    double ar3 = r * ar2;
-    double hi = t2 + ar2;
-    double lo3 = fsq_fma(ar, r, -ar2);
-    double lo4 = t2 - hi + ar2;
-    double p12 = fsq_fma(POW_A[2], r, POW_A[1]);
-    double p34 = fsq_fma(POW_A[4], r, POW_A[3]);
-    double p56 = fsq_fma(r, POW_A[6], POW_A[5]);
-    double q = fsq_fma(p56, ar2, p34);
-    q = fsq_fma(ar2, q, p12);
-    double lo = ((lo1 + lo2) + lo3) + lo4;
-    lo = fsq_fma(ar3, q, lo);
-    double y = hi + lo;
-    double tail = hi - y + lo;
-    double ehi = 2.0 * y;
-    double elo = fsq_fma(2.0, tail, fsq_fma(y, 2.0, -ehi));
-    return cs_exp_pow(ehi, elo);
-}
+// pow(x, 2.0) as glibc, with the exp tail inlined so that the kernels make no call (a call costs a scratch frame)
+__device__ __forceinline__ double cs_pow2(double x) { return sf_pow<2, true>(x); }
 
 // No input is a NaN, so a NaN result is one an invalid operation made (0 / 0 for R^2 of a flat trace, inf / inf).  The
 // reference ran on x86-64, whose default NaN has the sign bit set; the GPU's has not.  Results are compared bit for bit.

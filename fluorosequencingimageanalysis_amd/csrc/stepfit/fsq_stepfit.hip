@@ -13,6 +13,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_stepfit.h"
+#include "fsq_glibc_pow.h"
 #include "fsq_pairwise.h"
 
 namespace {
@@ -33,55 +34,8 @@ __device__ __forceinline__ bool trace_valid(const Cfg& c, int n)
     return Lm <= FSQ_STEPFIT_MAX_MIRRORED && !(c.ck && Lm <= 2);
 }
 
-// ---- pow(x, -2.0): glibc 2.35 pow (e_pow.c, FMA variant) for y = -2, x > 0 finite (the CK b_diff / f_diff) ------
-__device__ double sf_pow_m2(double x)
-{
-    unsigned long long ix = fsq_bits(x);
-    unsigned topx = (unsigned)(ix >> 52);
-    if (topx - 1u >= 0x7ffu - 1u) {
-        if (2 * ix - 1 >= 2 * 0x7ff0000000000000ull - 1) {            // 0, inf, nan
-            const double x2 = x * x;
-            if (2 * ix == 0) return __builtin_inf();                   // __math_divzero
-            return 1.0 / x2;                                           // inf -> 0, nan -> nan
-        }
-        ix &= 0x7fffffffffffffffull;
-        topx &= 0x7ff;
-        if (topx == 0) {                                               // subnormal x: normalise
-            ix = fsq_bits(fsq_dbl(ix) * 0x1p52);
-            ix &= 0x7fffffffffffffffull;
-            ix -= 52ull << 52;
-        }
-    }
-    unsigned long long tmp = ix - 0x3fe6955500000000ull;
-    int i = (int)((tmp >> 45) & 127);
-    int k = (int)((long long)tmp >> 52);
-    unsigned long long iz = ix - (tmp & (0xfffull << 52));
-    double z = fsq_dbl(iz), kd = (double)k;
-    double invc = FSQ_POW_LOG_TAB[i][0], logc = FSQ_POW_LOG_TAB[i][1], logctail = FSQ_POW_LOG_TAB[i][2];
-    double r = fsq_fma(z, invc, -1.0);
-    double t1 = fsq_fma(kd, POW_LN2HI, logc);
-    double t2 = t1 + r;
-    double lo1 = fsq_fma(kd, POW_LN2LO, logctail);
-    double lo2 = t1 - t2 + r;
-    double ar = POW_A[0] * r;
-    double ar2 = r * ar;
-    double ar3 = r * ar2;
-    double hi = t2 + ar2;
-    double lo3 = fsq_fma(ar, r, -ar2);
-    double lo4 = t2 - hi + ar2;
-    double p12 = fsq_fma(POW_A[2], r, POW_A[1]);
-    double p34 = fsq_fma(POW_A[4], r, POW_A[3]);
-    double p56 = fsq_fma(r, POW_A[6], POW_A[5]);
-    double q = fsq_fma(p56, ar2, p34);
-    q = fsq_fma(ar2, q, p12);
-    double lo = ((lo1 + lo2) + lo3) + lo4;
-    lo = fsq_fma(ar3, q, lo);
-    double y = hi + lo;
-    double tail = hi - y + lo;
-    double ehi = -2.0 * y;                                             // y * hi, y * lo + fma(y, hi, -ehi) for y = -2
-    double elo = fsq_fma(-2.0, tail, fsq_fma(y, -2.0, -ehi));
-    return fsq_exp_core<true>(ehi, elo);
-}
+// pow(x, -2.0) as glibc (the CK b_diff / f_diff); force-inlined, which is what the compiler made of the plain function before
+__device__ __forceinline__ double sf_pow_m2(double x) { return sf_pow<-2, false>(x); }
 
 // ---- two-sided Student t p-value: I_x(df/2, 1/2), x = df / (df + t^2) ---------------------------------------------
 // Continued fraction (modified Lentz) of the regularised incomplete beta function; 1 - x is formed as t^2 / (df + t^2).

@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from . import _native_chisq as NC
 from . import _native_stepfit as NS
 from . import engine as _engine
 
@@ -46,23 +47,35 @@ class PlateauTrace(object):
         return set(p[0] for p in self.trace)
 
 
-def _as_rows(photometries, photometry_min):
-    """Photometry sequences -> (float64 [n, max_frames] host rows, int32 lengths).  None frames count 0."""
-    if isinstance(photometries, np.ndarray) and photometries.ndim == 2:
-        seqs = [np.asarray(r, dtype=np.float64) for r in photometries]
+def _rows(sequences, none_is_zero, min_frames, nan_error):
+    """Sequences (a 2-D array or a list of ragged ones) -> (float64 [n, max_frames] host rows, int32 lengths).  nan_error: the
+    ValueError text (% the trace's index) for a sequence that holds a NaN, or None to let NaN pass."""
+    conv = (lambda v: 0.0 if v is None else float(v)) if none_is_zero else float
+    if isinstance(sequences, np.ndarray) and sequences.ndim == 2:
+        seqs = [np.asarray(r, dtype=np.float64) for r in sequences]
     else:
-        seqs = [np.array([0.0 if v is None else float(v) for v in s], dtype=np.float64) for s in photometries]
+        seqs = [np.array([conv(v) for v in s], dtype=np.float64) for s in sequences]
     lens = np.array([len(s) for s in seqs], dtype=np.int32)
-    if len(seqs) and lens.min() < 1:
+    if len(seqs) and lens.min() < min_frames:
         raise ValueError("every photometry trace needs at least one frame")
-    max_frames = int(lens.max()) if len(seqs) else 1
-    rows = np.zeros((len(seqs), max_frames), dtype=np.float64)
+    rows = np.zeros((len(seqs), max(int(lens.max()) if len(seqs) else 1, 1)), dtype=np.float64)
     for i, s in enumerate(seqs):
-        if photometry_min is None and np.isnan(s).any():
-            # (the reference's plateau comparisons depend on object identity with NaN heights: no pinnable result)
-            raise ValueError("trace %d holds a NaN photometry; pass photometry_min to clamp it" % i)
+        if nan_error is not None and np.isnan(s).any():
+            raise ValueError(nan_error % i)
         rows[i, :len(s)] = s
     return rows, lens
+
+
+def _as_rows(photometries, photometry_min):
+    """Photometry sequences -> (float64 [n, max_frames] host rows, int32 lengths).  None frames count 0."""
+    # (the reference's plateau comparisons depend on object identity with NaN heights: no pinnable result)
+    return _rows(photometries, True, 1,
+                 "trace %d holds a NaN photometry; pass photometry_min to clamp it" if photometry_min is None else None)
+
+
+def _lum_rows(sequences):
+    """Luminosity sequences -> (float64 [n, max_frames] host rows, int32 lengths); a NaN has no pinnable reference result."""
+    return _rows(sequences, False, 0, "trace %d holds a NaN luminosity")
 
 
 def _params(mirror_start, chung_kennedy, p_threshold, photometry_min, window_radius=LIVE_WINDOW_RADIUS, drop_sort=True,
@@ -99,6 +112,14 @@ def _check_lengths(lens, prm):
         raise ValueError("luminosities must have len(luminosities) > 2 for the Chung-Kennedy filter")
 
 
+def _plateau_out(n, max_frames, dev, zero, keys=("start", "stop", "height", "count")):
+    """The output tensors of one plateau list per trace under `keys`: zeros, or uninitialised where every row is written."""
+    torch = _engine._torch()
+    alloc = torch.zeros if zero else torch.empty
+    rows = [alloc((n, max_frames), dtype=dt, device=dev) for dt in (torch.int32, torch.int32, torch.float64)]
+    return dict(zip(keys, rows + [alloc(n, dtype=torch.int32, device=dev)]))
+
+
 def run_device(d_phot, d_len, max_frames, prm, want_p=False, pair_cap=0):
     """fsq_stepfit_traces on device tensors (float64 [n, max_frames], int32 [n]); returns a dict of device tensors:
     ck, pl_start, pl_stop, pl_h, pl_n, tf_start, tf_stop, tf_h, tf_n, status (and p when want_p; pair_p [n, pair_cap] and
@@ -115,10 +136,7 @@ def run_device(d_phot, d_len, max_frames, prm, want_p=False, pair_cap=0):
     n_radii = max(prm.window_radius - 5, 0)
     out = {"ck": torch.empty((n, max_frames), dtype=torch.float64, device=dev)}
     for pre in ("pl", "tf"):
-        out[pre + "_start"] = torch.empty((n, max_frames), dtype=torch.int32, device=dev)
-        out[pre + "_stop"] = torch.empty((n, max_frames), dtype=torch.int32, device=dev)
-        out[pre + "_h"] = torch.empty((n, max_frames), dtype=torch.float64, device=dev)
-        out[pre + "_n"] = torch.empty(n, dtype=torch.int32, device=dev)
+        out.update(_plateau_out(n, max_frames, dev, False, (pre + "_start", pre + "_stop", pre + "_h", pre + "_n")))
     out["status"] = torch.empty(n, dtype=torch.int32, device=dev)
     if want_p:
         out["p"] = torch.empty((n, n_radii, Lmax), dtype=torch.float64, device=dev)
@@ -161,12 +179,21 @@ def _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min,
     return host, lens, prm
 
 
-def _flat(host, pre):
-    cnt = host[pre + "_n"].astype(np.int64)
-    mask = np.arange(host[pre + "_start"].shape[1])[None, :] < cnt[:, None]
-    trace = np.nonzero(mask)[0].astype(np.int64)
-    return {"trace": trace, "start": host[pre + "_start"][mask], "stop": host[pre + "_stop"][mask], "height": host[pre + "_h"][mask],
+def _flat(start, stop, height, count):
+    """Plateau rows [n, max_frames] and counts [n] -> one entry per plateau, in trace order."""
+    cnt = count.astype(np.int64)
+    mask = np.arange(start.shape[1])[None, :] < cnt[:, None]
+    return {"trace": np.nonzero(mask)[0].astype(np.int64), "start": start[mask], "stop": stop[mask], "height": height[mask],
             "counts": cnt}
+
+
+def _flat_empty():
+    return _flat(np.zeros((0, 1), np.int32), np.zeros((0, 1), np.int32), np.zeros((0, 1)), np.zeros(0, np.int32))
+
+
+def _plateau_tuples(start, stop, height):
+    """The reference's (start, stop, height) plateaus: Python ints and np.float64 heights."""
+    return [(s, o, np.float64(h)) for s, o, h in zip(start.tolist(), stop.tolist(), height)]
 
 
 def stepfit_records(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, photometry_min=None, device=None):
@@ -177,16 +204,14 @@ def stepfit_records(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0
     and "lengths"."""
     host, lens, prm = _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min, device=device)
     if host is None:
-        empty = {"trace": np.zeros(0, np.int64), "start": np.zeros(0, np.int32), "stop": np.zeros(0, np.int32),
-                 "height": np.zeros(0), "counts": np.zeros(0, np.int64)}
-        return {"plateaus": empty, "t_filtered_plateaus": dict(empty), "ck_filtered": np.zeros((0, 1)), "lengths": lens}
-    return {"plateaus": _flat(host, "pl"), "t_filtered_plateaus": _flat(host, "tf"), "ck_filtered": host["ck"], "lengths": lens}
+        return {"plateaus": _flat_empty(), "t_filtered_plateaus": _flat_empty(), "ck_filtered": np.zeros((0, 1)), "lengths": lens}
+    flat = {pre: _flat(host[pre + "_start"], host[pre + "_stop"], host[pre + "_h"], host[pre + "_n"]) for pre in ("pl", "tf")}
+    return {"plateaus": flat["pl"], "t_filtered_plateaus": flat["tf"], "ck_filtered": host["ck"], "lengths": lens}
 
 
 def _plateau_lists(host, pre, i):
     n = int(host[pre + "_n"][i])
-    s, o, h = host[pre + "_start"][i, :n].tolist(), host[pre + "_stop"][i, :n].tolist(), host[pre + "_h"][i, :n]
-    return [(s[k], o[k], np.float64(h[k])) for k in range(n)]
+    return _plateau_tuples(host[pre + "_start"][i, :n], host[pre + "_stop"][i, :n], host[pre + "_h"][i, :n])
 
 
 def stepfit_photometries(photometries, mirror_start=0, chung_kennedy=0, p_threshold=0.01, photometry_min=None, keys=None,
@@ -235,42 +260,29 @@ def t_test_filter(luminosities, plateaus, p_threshold, drop_sort=True, no_merge_
     """stepfitting_library.t_test_filter (:1441-1480) on the GPU (fsq_stepfit_ttest_filter): merges adjacent plateaus whose
     Welch t-test p >= p_threshold, len(plateaus) - 1 passes, both the drop_sort and the left-to-right branch.  Plateaus
     must be consecutive (stop + 1 == next start) within the luminosities; unmerged plateaus keep their given heights."""
-    lum = np.array([0.0 if v is None else float(v) for v in luminosities], dtype=np.float64)
-    pls = [(int(a), int(o), float(h)) for a, o, h in plateaus]
-    if len(pls) < 2:
+    d = _plateau_rows(luminosities, plateaus, "t_test_filter", lenient=True)
+    if d is None:
         return list(plateaus)
-    n = len(lum)
-    if n > NS.MAX_MIRRORED:
-        raise ValueError("t_test_filter: at most %d luminosities" % NS.MAX_MIRRORED)
-    if not (0 <= pls[0][0] and pls[-1][1] < n and all(a <= o for a, o, _ in pls) and
-            all(pls[i][1] + 1 == pls[i + 1][0] for i in range(len(pls) - 1))):
-        raise ValueError("Merged plateaus must be consecutive and lie within the luminosities")
     torch = _engine._torch()
-    dev = torch.device("cuda")
+    dev, n = d["lum"].device, int(d["lum"].shape[1])
     L = NS.lib()
     ws_bytes = L.fsq_stepfit_ttest_filter_workspace_bytes(1, n)
-    st = np.zeros((1, n), np.int32); so = np.zeros((1, n), np.int32); hh = np.zeros((1, n))
-    st[0, :len(pls)] = [a for a, _, _ in pls]; so[0, :len(pls)] = [o for _, o, _ in pls]; hh[0, :len(pls)] = [h for _, _, h in pls]
-    d = {k: torch.from_numpy(v).to(dev) for k, v in (("lum", lum[None]), ("len", np.array([n], np.int32)), ("s", st), ("o", so),
-                                                       ("h", hh), ("n", np.array([len(pls)], np.int32)))}
-    out = {"s": torch.empty((1, n), dtype=torch.int32, device=dev), "o": torch.empty((1, n), dtype=torch.int32, device=dev),
-           "h": torch.empty((1, n), dtype=torch.float64, device=dev), "n": torch.empty(1, dtype=torch.int32, device=dev),
-           "st": torch.empty(1, dtype=torch.int32, device=dev)}
+    out = _plateau_out(1, n, dev, False)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
     rc = L.fsq_stepfit_ttest_filter(d["lum"].data_ptr(), d["len"].data_ptr(), 1, n, d["s"].data_ptr(), d["o"].data_ptr(),
                                     d["h"].data_ptr(), d["n"].data_ptr(), float(p_threshold), 1 if drop_sort else 0,
-                                    int(no_merge_start), out["s"].data_ptr(), out["o"].data_ptr(), out["h"].data_ptr(),
-                                    out["n"].data_ptr(), out["st"].data_ptr(), None, None, 0, ws.data_ptr(), int(ws_bytes),
+                                    int(no_merge_start), out["start"].data_ptr(), out["stop"].data_ptr(), out["height"].data_ptr(),
+                                    out["count"].data_ptr(), status.data_ptr(), None, None, 0, ws.data_ptr(), int(ws_bytes),
                                     torch.cuda.current_stream(dev).cuda_stream)
     N.check(rc, "fsq_stepfit_ttest_filter")
-    h = {k: v.cpu().numpy() for k, v in out.items()}
-    if h["st"][0] == NS.STATUS_UNSUPPORTED:
+    st = int(status.cpu()[0])
+    if st == NS.STATUS_UNSUPPORTED:
         raise NotImplementedError("t_test_filter: a pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
                                   "is not restated)")
-    if h["st"][0] != NS.STATUS_OK:
+    if st != NS.STATUS_OK:
         raise ValueError("t_test_filter: invalid plateaus")
-    k = int(h["n"][0])
-    return [(int(h["s"][0, i]), int(h["o"][0, i]), np.float64(h["h"][0, i])) for i in range(k)]
+    return _first_plateaus(out)
 
 
 def refit_plateaus(luminosities, plateaus):
@@ -311,7 +323,6 @@ def unmirror_plateaus(plateaus, mirror_size):
 # ---- chi-squared step fitter, plateau merge filters, R^2 (include/fsq_chisq.h) --------------------------------------------
 def _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits):
     """FsqChisqParams after the reference's own argument check (:433-435)."""
-    from . import _native_chisq as NC
     if not 0 < num_steps_multiplier <= 1:
         raise ValueError("num_steps_multiplier has an invalid value of " + str(num_steps_multiplier))
     if num_steps is not None and not 0 < num_steps:
@@ -331,7 +342,6 @@ def chisq_device(d_lum, d_len, num_steps_multiplier=1, num_steps=None, min_step_
     start, stop, height [n, max_frames], count, n_fits, status [n] and, when fit_cap > 0, best_res, counter_res, S
     (float64 [n, fit_cap]) and counter_n (int32).  Enqueued on the current stream, not synchronised.  Lengths are not
     checked here: a trace the device refuses comes back with a status other than 0 and its rows as allocated (zeros)."""
-    from . import _native_chisq as NC
     torch = _engine._torch()
     prm = _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits)
     dev = d_lum.device
@@ -340,11 +350,8 @@ def chisq_device(d_lum, d_len, num_steps_multiplier=1, num_steps=None, min_step_
     ws_bytes = L.fsq_chisq_workspace_bytes(n, max_frames)
     if ws_bytes < 0:
         raise ValueError("fsq_chisq_workspace_bytes: invalid shape")
-    out = {"start": torch.zeros((n, max_frames), dtype=torch.int32, device=dev),
-           "stop": torch.zeros((n, max_frames), dtype=torch.int32, device=dev),
-           "height": torch.zeros((n, max_frames), dtype=torch.float64, device=dev),
-           "count": torch.zeros(n, dtype=torch.int32, device=dev), "n_fits": torch.zeros(n, dtype=torch.int32, device=dev),
-           "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    out = _plateau_out(n, max_frames, dev, True)
+    out["n_fits"], out["status"] = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
     if fit_cap > 0:
         for k in ("best_res", "counter_res", "S"):
             out[k] = torch.zeros((n, fit_cap), dtype=torch.float64, device=dev)
@@ -360,21 +367,6 @@ def chisq_device(d_lum, d_len, num_steps_multiplier=1, num_steps=None, min_step_
     return out
 
 
-def _lum_rows(sequences):
-    """Luminosity sequences -> (float64 [n, max_frames] host rows, int32 lengths); a NaN has no pinnable reference result."""
-    if isinstance(sequences, np.ndarray) and sequences.ndim == 2:
-        seqs = [np.asarray(r, dtype=np.float64) for r in sequences]
-    else:
-        seqs = [np.array([float(v) for v in s], dtype=np.float64) for s in sequences]
-    lens = np.array([len(s) for s in seqs], dtype=np.int32)
-    rows = np.zeros((len(seqs), max(int(lens.max()) if len(seqs) else 1, 1)), dtype=np.float64)
-    for i, s in enumerate(seqs):
-        if np.isnan(s).any():
-            raise ValueError("trace %d holds a NaN luminosity" % i)
-        rows[i, :len(s)] = s
-    return rows, lens
-
-
 def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step_length=2, min_step_magnitude=0.0,
                   ignore_counterfits=False, fit_cap=0, device=None):
     """chi_squared_step_fitter for many traces in one launch, as arrays.
@@ -382,7 +374,6 @@ def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step
     Returns a dict: "trace", "start", "stop", "height" (one entry per plateau, in trace order), "counts" and "n_fits" per
     trace, "lengths" and, when fit_cap > 0, "best_res", "counter_res", "S", "counter_n" ([n, fit_cap], row t valid up to
     n_fits[t]).  Raises the reference's errors for the first trace that has one."""
-    from . import _native_chisq as NC
     rows, lens = _lum_rows(photometries)
     _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits)
     if len(lens) and lens.max() > NC.MAX_FRAMES:
@@ -393,8 +384,7 @@ def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step
         if num_steps is None and n < 2:
             raise IndexError("list index out of range")            # (the reference sorts an empty list of fits, :502)
     if len(lens) == 0:
-        return {"trace": np.zeros(0, np.int64), "start": np.zeros(0, np.int32), "stop": np.zeros(0, np.int32),
-                "height": np.zeros(0), "counts": np.zeros(0, np.int64), "n_fits": np.zeros(0, np.int32), "lengths": lens}
+        return dict(_flat_empty(), n_fits=np.zeros(0, np.int32), lengths=lens)
     torch = _engine._torch()
     dev = torch.device(device or "cuda")
     out = chisq_device(torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev), num_steps_multiplier, num_steps,
@@ -406,10 +396,7 @@ def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step
         raise ValueError("num_plateaus = " + str(int(lens[i]) + 1) + " is greater than len(luminosities) = " + str(int(lens[i])))
     if (st != NS.STATUS_OK).any():
         raise ValueError("trace %d: invalid length or num_steps" % int(np.flatnonzero(st != NS.STATUS_OK)[0]))
-    cnt = host["count"].astype(np.int64)
-    mask = np.arange(rows.shape[1])[None, :] < cnt[:, None]
-    res = {"trace": np.nonzero(mask)[0].astype(np.int64), "start": host["start"][mask], "stop": host["stop"][mask],
-           "height": host["height"][mask], "counts": cnt, "n_fits": host["n_fits"], "lengths": lens}
+    res = dict(_flat(host["start"], host["stop"], host["height"], host["count"]), n_fits=host["n_fits"], lengths=lens)
     for k in ("best_res", "counter_res", "S", "counter_n"):
         if k in host:
             res[k] = host[k]
@@ -421,14 +408,19 @@ def chi_squared_step_fitter(luminosity_sequence, num_steps_multiplier=1, num_ste
     """stepfitting_library.chi_squared_step_fitter (:342-505) on the GPU: a list of (start, stop, height) plateaus."""
     r = chisq_records([luminosity_sequence], num_steps_multiplier, num_steps, min_step_length, min_step_magnitude,
                       ignore_counterfits)
-    return [(int(s), int(o), np.float64(h)) for s, o, h in zip(r["start"], r["stop"], r["height"])]
+    return _plateau_tuples(r["start"], r["stop"], r["height"])
 
 
-def _plateau_rows(luminosities, plateaus, what):
-    lum = np.array([float(v) for v in luminosities], dtype=np.float64)
-    if np.isnan(lum).any():
+def _plateau_rows(luminosities, plateaus, what, lenient=False):
+    """One trace and its plateaus as the device rows of the filter kernels: {"lum", "len", "s", "o", "h", "n"}.  lenient
+    (t_test_filter): None luminosities count 0, NaN ones pass, and fewer than two plateaus give None (nothing to merge)."""
+    conv = (lambda v: 0.0 if v is None else float(v)) if lenient else float
+    lum = np.array([conv(v) for v in luminosities], dtype=np.float64)
+    if not lenient and np.isnan(lum).any():
         raise ValueError(what + ": a NaN luminosity")
     pls = [(int(a), int(o), float(h)) for a, o, h in plateaus]
+    if lenient and len(pls) < 2:
+        return None
     n = len(lum)
     if n > NS.MAX_MIRRORED:
         raise ValueError(what + ": at most %d luminosities" % NS.MAX_MIRRORED)
@@ -439,21 +431,24 @@ def _plateau_rows(luminosities, plateaus, what):
     st[0, :len(pls)] = [a for a, _, _ in pls]; so[0, :len(pls)] = [o for _, o, _ in pls]; hh[0, :len(pls)] = [h for _, _, h in pls]
     torch = _engine._torch()
     dev = torch.device("cuda")
-    d = {k: torch.from_numpy(v).to(dev) for k, v in (("lum", lum[None]), ("len", np.array([n], np.int32)), ("s", st), ("o", so),
-                                                       ("h", hh), ("n", np.array([len(pls)], np.int32)))}
-    return d, n, dev, torch
+    return {k: torch.from_numpy(v).to(dev) for k, v in (("lum", lum[None]), ("len", np.array([n], np.int32)), ("s", st), ("o", so),
+                                                          ("h", hh), ("n", np.array([len(pls)], np.int32)))}
+
+
+def _first_plateaus(out):
+    """Trace 0 of the "start", "stop", "height", "count" device tensors as the reference's plateau tuples."""
+    k = int(out["count"].cpu()[0])
+    return _plateau_tuples(*(out[key][0, :k].cpu().numpy() for key in ("start", "stop", "height")))
 
 
 def merge_filter_device(d_lum, d_len, d_start, d_stop, d_h, d_n, mode, min_magnitude=None, min_noise_ratio=None):
     """fsq_stepfit_merge_filter on device tensors (rows of [n, max_frames]); mode 0 filter_upsteps, 1 filter_small_steps.
     Returns {"start", "stop", "height", "count", "status"} device tensors; enqueued on the current stream."""
-    from . import _native_chisq as NC
     torch = _engine._torch()
     dev = d_lum.device
     n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
-    out = {"start": torch.zeros((n, mf), dtype=torch.int32, device=dev), "stop": torch.zeros((n, mf), dtype=torch.int32, device=dev),
-           "height": torch.zeros((n, mf), dtype=torch.float64, device=dev), "count": torch.zeros(n, dtype=torch.int32, device=dev),
-           "status": torch.zeros(n, dtype=torch.int32, device=dev)}
+    out = _plateau_out(n, mf, dev, True)
+    out["status"] = torch.zeros(n, dtype=torch.int32, device=dev)
     rc = NC.lib().fsq_stepfit_merge_filter(d_lum.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
                                            d_h.data_ptr(), d_n.data_ptr(), int(mode), 0 if min_magnitude is None else 1,
                                            0.0 if min_magnitude is None else float(min_magnitude),
@@ -467,7 +462,6 @@ def merge_filter_device(d_lum, d_len, d_start, d_stop, d_h, d_n, mode, min_magni
 
 def r_squared_device(d_lum, d_len, d_start, d_stop, d_h, d_n):
     """fsq_stepfit_r_squared on device tensors; returns {"r2", "status"} device tensors."""
-    from . import _native_chisq as NC
     torch = _engine._torch()
     dev = d_lum.device
     n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
@@ -482,13 +476,11 @@ def r_squared_device(d_lum, d_len, d_start, d_stop, d_h, d_n):
 def _merge_filter(luminosities, plateaus, mode, min_magnitude, min_noise_ratio, what):
     if len(plateaus) < 2:
         return list(plateaus)
-    d, n, dev, torch = _plateau_rows(luminosities, plateaus, what)
+    d = _plateau_rows(luminosities, plateaus, what)
     out = merge_filter_device(d["lum"], d["len"], d["s"], d["o"], d["h"], d["n"], mode, min_magnitude, min_noise_ratio)
-    h = {k: v.cpu().numpy() for k, v in out.items()}
-    if h["status"][0] != NS.STATUS_OK:
+    if int(out["status"].cpu()[0]) != NS.STATUS_OK:
         raise ValueError(what + ": invalid plateaus")
-    k = int(h["count"][0])
-    return [(int(h["start"][0, i]), int(h["stop"][0, i]), np.float64(h["height"][0, i])) for i in range(k)]
+    return _first_plateaus(out)
 
 
 def filter_upsteps(luminosities, plateaus):
@@ -508,7 +500,7 @@ def filter_small_steps(luminosities, plateaus, min_magnitude=None, min_noise_rat
 
 def stepfit_r_squared(luminosities, plateaus):
     """stepfitting_library.stepfit_r_squared (:1483-1503) on the GPU: 1 - SS_res / SS_tot over the frames the plateaus span."""
-    d, n, dev, torch = _plateau_rows(luminosities, plateaus, "stepfit_r_squared")
+    d = _plateau_rows(luminosities, plateaus, "stepfit_r_squared")
     out = r_squared_device(d["lum"], d["len"], d["s"], d["o"], d["h"], d["n"])
     if int(out["status"].cpu()[0]) != NS.STATUS_OK:
         raise ValueError("stepfit_r_squared: invalid plateaus")

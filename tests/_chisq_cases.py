@@ -6,10 +6,6 @@ import numpy as np
 from _util import GOLD
 
 
-def _bits(a):
-    return np.asarray(a, dtype=np.float64).view(np.uint64)
-
-
 def golden():
     return np.load(os.path.join(GOLD, "chisq_traces.npz"))
 
@@ -39,11 +35,6 @@ def filter_cases():
                         pin=list(zip(g["fin_start"][im].tolist(), g["fin_stop"][im].tolist(), g["fin_h"][im].tolist())),
                         pout=list(zip(g["fout_start"][om].tolist(), g["fout_stop"][om].tolist(), g["fout_h"][om].tolist()))))
     return out
-
-
-def same_plateaus(got, exp, what=None):
-    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp], what
-    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp])), what
 
 
 # parameter sets of the random batch: (num_steps, multiplier, min_step_length, min_step_magnitude, ignore_counterfits)

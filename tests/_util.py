@@ -55,3 +55,13 @@ def bits_equal(a, b):
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
     return (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+
+
+def _bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same_plateaus(got, exp, what=None):
+    """Plateau lists with equal (start, stop) and bit-identical heights."""
+    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp], what
+    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp])), what

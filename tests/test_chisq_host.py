@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import _chisq_reference as R
-from _chisq_cases import _bits, filter_cases, fit_cases, golden, same_plateaus
-from _util import ROOT
+from _chisq_cases import filter_cases, fit_cases, golden
+from _util import ROOT, _bits, same_plateaus
 
 
 def test_fixture_is_not_vacuous():

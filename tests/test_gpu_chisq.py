@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 import _chisq_reference as R
-from _chisq_cases import BATCH_PARAMS, _bits, filter_cases, fit_cases, random_batch, same_plateaus
+from _chisq_cases import BATCH_PARAMS, filter_cases, fit_cases, random_batch
+from _util import _bits, same_plateaus
 
 pytestmark = pytest.mark.gpu
 

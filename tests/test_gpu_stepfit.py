@@ -4,14 +4,10 @@ import numpy as np
 import pytest
 
 import _stepfit_reference as R
-from test_stepfit_host import _bits, check_pair_p, golden_cases, timetrace_golden
+from _util import _bits, same_plateaus
+from test_stepfit_host import check_pair_p, golden_cases, timetrace_golden
 
 pytestmark = pytest.mark.gpu
-
-
-def _same_plateaus(got, exp):
-    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp]
-    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp]))
 
 
 def _run_case(c, want_p=False):
@@ -33,7 +29,7 @@ def test_golden_through_c_abi():
         for pre, key in (("pl", "pl"), ("tf", "tf")):
             k = int(h[pre + "_n"][0])
             got = list(zip(h[pre + "_start"][0, :k], h[pre + "_stop"][0, :k], h[pre + "_h"][0, :k]))
-            _same_plateaus(got, c[key])
+            same_plateaus(got, c[key])
         Lm = n + min(c["mirror"], n)
         n_radii = max(c["wr"] - 5, 0)
         p = h["p"][0][:, :Lm].reshape(-1) if n_radii else np.zeros(0)
@@ -56,8 +52,8 @@ def test_golden_through_python_api():
         assert (ph.h, ph.w, tf.h, tf.w) == (4, 5, 4, 5)
         assert np.array_equal(_bits(ph.trace), _bits(c["phot_out"])), i
         assert np.array_equal(_bits(ck.trace), _bits(c["ck_out"])), i
-        _same_plateaus(pl.trace, c["pl"])
-        _same_plateaus(tf.trace, c["tf"])
+        same_plateaus(pl.trace, c["pl"])
+        same_plateaus(tf.trace, c["tf"])
 
 
 def test_golden_records_batch():
@@ -72,7 +68,7 @@ def test_golden_records_batch():
             t = r[key]
             for j, c in enumerate(sel):
                 m = t["trace"] == j
-                _same_plateaus(list(zip(t["start"][m], t["stop"][m], t["height"][m])), c["pl" if key == "plateaus" else "tf"])
+                same_plateaus(list(zip(t["start"][m], t["stop"][m], t["height"][m])), c["pl" if key == "plateaus" else "tf"])
 
 
 def _random_traces(rng, n_traces, max_len):
@@ -102,7 +98,7 @@ def _check_sample(traces, idx, r, opts):
         for key, exp in (("plateaus", pl), ("t_filtered_plateaus", tf)):
             T = r[key]
             m = T["trace"] == j
-            _same_plateaus(list(zip(T["start"][m], T["stop"][m], T["height"][m])), exp)
+            same_plateaus(list(zip(T["start"][m], T["stop"][m], T["height"][m])), exp)
         checked += 1
     return checked
 
@@ -145,7 +141,7 @@ def test_drop_ins():
     fl = R.Flags()
     steps = R.sliding_steps(v, 20, 0.001, fl)
     if not fl.near:
-        _same_plateaus(S.sliding_t_fitter(v.tolist()), R.plateaus_from_steps(steps, len(v), v))
+        same_plateaus(S.sliding_t_fitter(v.tolist()), R.plateaus_from_steps(steps, len(v), v))
     exp = R.ck_filter(v.tolist(), window_lengths=tuple(range(2, 17)))
     assert np.array_equal(_bits(S.chung_kennedy_filter(v.tolist())), _bits(exp))
 
@@ -180,7 +176,7 @@ def test_timetrace_experiment_golden():
         assert np.array_equal(_bits(d["ck_filtered_photometries"].trace), _bits(g["ck_filtered"][k]))
         for pre, name in (("pl", "plateaus"), ("tf", "t_filtered_plateaus")):
             m = g[pre + "_trace"] == k
-            _same_plateaus(d[name].trace, list(zip(g[pre + "_start"][m], g[pre + "_stop"][m], g[pre + "_h"][m])))
+            same_plateaus(d[name].trace, list(zip(g[pre + "_start"][m], g[pre + "_stop"][m], g[pre + "_h"][m])))
         assert (d["plateaus"].h, d["plateaus"].w) == key
 
 
@@ -199,7 +195,7 @@ def test_t_test_filter_drop_in(drop_sort):
         exp = R.t_test_filter(tr, pl, 0.01, drop_sort=drop_sort, no_merge_start=nms, flags=fl)
         if fl.near or exp is None:
             continue
-        _same_plateaus(S.t_test_filter(tr.tolist(), pl, 0.01, drop_sort=drop_sort, no_merge_start=nms), exp)
+        same_plateaus(S.t_test_filter(tr.tolist(), pl, 0.01, drop_sort=drop_sort, no_merge_start=nms), exp)
         checked += 1
     assert checked >= 120
 
@@ -239,6 +235,6 @@ def test_random_traces_other_options(wr, drop_sort, nan):
         assert np.array_equal(_bits(h["ck"][j, :len(ck)]), _bits(ck))
         for pre, exp in (("pl", pl), ("tf", tf)):
             k = int(h[pre + "_n"][j])
-            _same_plateaus(list(zip(h[pre + "_start"][j, :k], h[pre + "_stop"][j, :k], h[pre + "_h"][j, :k])), exp)
+            same_plateaus(list(zip(h[pre + "_start"][j, :k], h[pre + "_stop"][j, :k], h[pre + "_h"][j, :k])), exp)
         checked += 1
     assert checked >= 90

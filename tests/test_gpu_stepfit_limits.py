@@ -20,6 +20,7 @@ import pytest
 
 import _limits_cases as LC
 import _stepfit_reference as R
+from _util import _bits, same_plateaus
 from test_limits_host import param_limit_expected
 from test_stepfit_host import check_pair_p
 
@@ -27,15 +28,6 @@ pytestmark = pytest.mark.gpu
 
 INVALID = 2
 SENT_I, SENT_F = -777, -777.25
-
-
-def _bits(a):
-    return np.asarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_plateaus(got, exp):
-    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp]
-    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp]))
 
 
 def _rows(traces, max_frames=None):
@@ -145,8 +137,8 @@ def test_length_limits_equal_reference_records():
             assert np.array_equal(_bits(h["ck"][0, :n]), _bits(c["ck_out"])), i
         else:
             assert np.array_equal(_bits(h["ck"][0, :n]), _bits(c["phot"])), i
-        _same_plateaus(_plateaus(h, "pl", 0), c["pl"])
-        _same_plateaus(_plateaus(h, "tf", 0), c["tf"])
+        same_plateaus(_plateaus(h, "pl", 0), c["pl"])
+        same_plateaus(_plateaus(h, "tf", 0), c["tf"])
         k = int(h["pair_n"][0])
         assert k >= 1
         check_pair_p(h["pair_p"][0, :k], c["p_pairs"])
@@ -273,8 +265,8 @@ def test_parameter_limits_equal_restatement(name):
             continue
         ckf, pl, tf = e
         assert np.array_equal(_bits(h["ck"][j, :len(ckf)]), _bits(ckf)), j
-        _same_plateaus(_plateaus(h, "pl", j), pl)
-        _same_plateaus(_plateaus(h, "tf", j), tf)
+        same_plateaus(_plateaus(h, "pl", j), pl)
+        same_plateaus(_plateaus(h, "tf", j), tf)
         checked += 1
     assert checked >= (1.0 - LC.MAX_SKIPPED_SHARE) * len(traces)
 
@@ -298,12 +290,12 @@ def test_sort_paths_with_ties_and_nan():
                 exp = R.t_test_filter(lum, pl, LC.SORT_THR, drop_sort=ds, no_merge_start=nms, flags=fl)
                 assert not fl.near and not fl.unsupported and out["st"][j] == 0, k
                 m = int(out["n"][j])
-                _same_plateaus(list(zip(out["s"][j, :m], out["o"][j, :m], out["h"][j, :m])), exp)
+                same_plateaus(list(zip(out["s"][j, :m], out["o"][j, :m], out["h"][j, :m])), exp)
                 assert (out["h"][j, m:] == SENT_F).all(), k
                 q = min(int(out["pair_n"][j]), cap)
                 assert int(out["pair_n"][j]) == len(fl.p_pairs), k
                 check_pair_p(out["pair_p"][j, :q], fl.p_pairs[:q])
-                _same_plateaus(S.t_test_filter(lum.tolist(), pl, LC.SORT_THR, drop_sort=ds, no_merge_start=nms), exp)
+                same_plateaus(S.t_test_filter(lum.tolist(), pl, LC.SORT_THR, drop_sort=ds, no_merge_start=nms), exp)
 
 
 # ---- A5 ------------------------------------------------------------------------------------------------------------------------
@@ -349,4 +341,4 @@ def test_invalid_rows_leave_their_neighbours_alone(ck):
             n = int(lens[j])
             assert np.array_equal(_bits(dev["ck"][j, :n]), _bits(clean["ck"][i, :n])), j
             for pre in ("pl", "tf"):
-                _same_plateaus(_plateaus(dev, pre, j), _plateaus(clean, pre, i))
+                same_plateaus(_plateaus(dev, pre, j), _plateaus(clean, pre, i))

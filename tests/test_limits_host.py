@@ -11,15 +11,7 @@ import pytest
 import _limits_cases as LC
 import _sequence_reference as Q
 import _stepfit_reference as R
-
-
-def _bits(a):
-    return np.asarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_plateaus(got, exp):
-    assert [(int(s), int(o)) for s, o, _ in got] == [(int(s), int(o)) for s, o, _ in exp]
-    assert np.array_equal(_bits([h for _, _, h in got]), _bits([h for _, _, h in exp]))
+from _util import _bits, same_plateaus
 
 
 # ---- A1 ------------------------------------------------------------------------------------------------------------------------
@@ -36,8 +28,8 @@ def test_length_limit_fixture_equals_restatement():
         assert not fl.near and not fl.unsupported, i
         if c["ck"]:
             assert np.array_equal(_bits(ck), _bits(c["ck_out"])), i
-        _same_plateaus(pl, c["pl"])
-        _same_plateaus(tf, c["tf"])
+        same_plateaus(pl, c["pl"])
+        same_plateaus(tf, c["tf"])
         if c["thr"] < 0.01:
             lens = [o - s + 1 for s, o, _ in c["tf"]]
             assert max(lens) > 7689 and sum(1 for x in lens if 129 < x <= 7689) >= 3, i

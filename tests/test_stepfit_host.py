@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import _stepfit_reference as R
-from _util import GOLD, ROOT
+from _util import GOLD, ROOT, _bits
 
 
 def golden_cases():
@@ -28,10 +28,6 @@ def golden_cases():
                         wr=int(g["case_wr"][i]), drop_sort=bool(g["case_drop_sort"][i]), thr=float(g["case_thr"][i]),
                         pmin=float(g["case_pmin"][i]) if g["case_has_min"][i] else None))
     return out
-
-
-def _bits(a):
-    return np.asarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_restatement_bit_identical_to_golden():
