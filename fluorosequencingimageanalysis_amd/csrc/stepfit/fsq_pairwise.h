@@ -38,13 +38,15 @@ __device__ double pw_sum(const G& g, int off, int n)
         return pw_sum<D - 1>(g, off, n2) + pw_sum<D - 1>(g, off + n2, n - n2);
     }
 }
+// np.mean: np.add.reduce starts from the identity +0.0 and adds the pairwise sum to it, so frames that are all -0.0 have the
+// mean +0.0 (the sum alone would be -0.0 from 8 frames on, where the accumulators start from the frames themselves)
 __device__ __forceinline__ double np_mean_short(const double* a, int n)      // n <= 128
 {
-    return pw_leaf([a](int i) { return a[i]; }, 0, n) / (double)n;
+    return (0.0 + pw_leaf([a](int i) { return a[i]; }, 0, n)) / (double)n;
 }
 __device__ double np_mean(const double* a, int n)
 {
-    return pw_sum<8>([a](int i) { return a[i]; }, 0, n) / (double)n;
+    return (0.0 + pw_sum<8>([a](int i) { return a[i]; }, 0, n)) / (double)n;
 }
 
 // The same sum without calls: each level is a two-trip loop over its halves, so a call site holds D + 1 copies of the
@@ -70,7 +72,7 @@ __device__ __forceinline__ double pw_sum_flat(const G& g, int off, int n)
 template <int D>
 __device__ __forceinline__ double np_mean_flat(const double* a, int n)
 {
-    return pw_sum_flat<D>([a](int i) { return a[i]; }, 0, n) / (double)n;
+    return (0.0 + pw_sum_flat<D>([a](int i) { return a[i]; }, 0, n)) / (double)n;
 }
 
 }  // namespace

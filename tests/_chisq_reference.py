@@ -120,9 +120,10 @@ def _res_sum(plateaus):
 
 
 def chi_squared(lum, num_steps_multiplier=1, num_steps=None, min_step_length=2, min_step_magnitude=0.0,
-                ignore_counterfits=False):
+                ignore_counterfits=False, records=None):
     """chi_squared_step_fitter.  Returns (fit, records): the list of (start, stop, height) and, for every plateau count
-    tried, (best-fit residual sum, counter-fit residual sum, counter-fit plateau count, S)."""
+    tried, (best-fit residual sum, counter-fit residual sum, counter-fit plateau count, S).  A caller's `records` list is
+    appended to, so that it holds the fits tried when the reference's ValueError is raised."""
     n = len(lum)
     if not 0 < num_steps_multiplier <= 1:
         raise ValueError("num_steps_multiplier has an invalid value of " + str(num_steps_multiplier))
@@ -136,7 +137,7 @@ def chi_squared(lum, num_steps_multiplier=1, num_steps=None, min_step_length=2, 
     L = max(int(min_step_length), 0)
     h = T.mean(0, n - 1)
     first = [(0, n - 1, h, residual(T.arr, 0, n - 1, h))]
-    fits, records = [], []
+    fits, records = [], ([] if records is None else records)
     best = None
     for p in range(1, num_steps + 2):
         if best is None:

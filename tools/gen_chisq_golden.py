@@ -11,6 +11,17 @@ residual sums change when `** 2` is replaced by a plain multiply, at least 5 cas
 (`<=` inside a plateau, `<` across plateaus), and at least 5 cases have a counter-fit count different from p + 1.
 
   python tools/gen_chisq_golden.py [--reference DIR]
+
+--limits writes tests/golden/chisq_limits.npz instead: the cases of tests/_chisq_limit_cases.recorded_cases() through the
+reference, recorded the same way (fit and per-p records), in about three minutes.  Reference-recorded are every extreme-scale
+case (1e-165 .. 1e154, the 2^52 and 1e15 offsets, the -0.0 / +0.0 mixes, each with num_steps 5 and None), the reduced long
+cases (LONG_CASES_RECORDED: 300 frames with 31 and 37 fits, 130 frames with 31 plateaus, the pairwise split lengths 129 / 136 /
+257 with num_steps 8) and the full-size long cases of RECORDED_FULL (300 frames with 105 fits, 130 frames with 129 plateaus,
+520 frames, 1 024 frames with num_steps 80).  The reference is pure Python without caching; the other full-size cases of
+LONG_CASES (1 024 frames with 104 fits and counter-fits of 104 plateaus, 700 and 1 023 frames) are carried by the restatement,
+which tests/test_chisq_limits_host.py pins to these records.
+
+  python tools/gen_chisq_golden.py --limits [--reference DIR]
 """
 import argparse
 import os
@@ -90,17 +101,72 @@ def fit_cases():
     return cases
 
 
+def record_limits(sf, out_path):
+    """tests/golden/chisq_limits.npz: fit and per-p records of tests/_chisq_limit_cases.recorded_cases()."""
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _chisq_limit_cases as CL
+    log = []
+    real_fit_steps = sf._fit_steps
+
+    def fit_steps_rec(*args, **kw):
+        r = real_fit_steps(*args, **kw)
+        log.append((kw.get("bestfit_plateaus") is not None, list(r)))
+        return r
+    sf._fit_steps = fit_steps_rec
+    meta = {k: [] for k in ("len", "num_steps", "mult", "L")}
+    names, lum_flat, lum_off, fit_rows, rec_rows = [], [], [0], [], []
+    t_all = time.time()
+    for ci, (name, v, ns, mult, L) in enumerate(CL.recorded_cases()):
+        lum = [float(x) for x in v]
+        del log[:]
+        t0 = time.time()
+        with np.errstate(all="ignore"):
+            fit = sf.chi_squared_step_fitter(lum, num_steps_multiplier=mult, num_steps=ns, min_step_length=L)
+            k = p = 0
+            while k + 1 < len(log):
+                assert not log[k][0] and log[k + 1][0]
+                best, counter = log[k][1], log[k + 1][1]
+                p += 1
+                assert len(best) == p
+                br = np.float64(sf._plateaus_squared_residuals(lum, best))
+                cr = np.float64(sf._plateaus_squared_residuals(lum, counter))
+                rec_rows.append((ci, float(br), float(cr), len(counter), float(cr / br) if br != 0 else 1e10))
+                k += 2
+        names.append(name)
+        meta["len"].append(len(lum)); meta["num_steps"].append(0 if ns is None else ns); meta["mult"].append(mult); meta["L"].append(L)
+        lum_flat.extend(lum); lum_off.append(len(lum_flat))
+        fit_rows += [(ci, s, o, float(h)) for s, o, h in fit]
+        print("case %d %s: n=%d num_steps=%s mult=%g L=%d -> %d plateaus, %d fits tried, %.1f s" %
+              (ci, name, len(lum), ns, mult, L, len(fit), p, time.time() - t0), flush=True)
+    sf._fit_steps = real_fit_steps
+    out = {"case_name": np.array(names), "lum": np.array(lum_flat), "lum_off": np.array(lum_off, dtype=np.int64)}
+    for k, v in meta.items():
+        out["case_" + k] = np.array(v, dtype=np.float64 if k == "mult" else np.int64)
+    for pre, rows, cols in (("fit", fit_rows, (("case", True), ("start", True), ("stop", True), ("h", False))),
+                            ("rec", rec_rows, (("case", True), ("best", False), ("counter", False), ("counter_n", True), ("S", False)))):
+        for j, (c, integer) in enumerate(cols):
+            col = np.array([r[j] for r in rows], dtype=np.float64)
+            out[pre + "_" + c] = col.astype(np.int64) if integer else col
+    np.savez_compressed(out_path, **out)
+    print("wrote", out_path, os.path.getsize(out_path), "bytes, %.0f s" % (time.time() - t_all))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default=os.environ.get("FSQ_REFERENCE", "/root/reference"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "chisq_traces.npz"))
+    ap.add_argument("--limits", action="store_true", help="write tests/golden/chisq_limits.npz instead")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "tests", "golden", "chisq_limits.npz" if a.limits else "chisq_traces.npz")
     os.environ["FSQ_REFERENCE"] = a.reference
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import refload
     refload.REF = a.reference
     refload.load_reference()
     sf = refload.load("stepfitting_library", "stepfitting_library.py")
+    if a.limits:
+        return record_limits(sf, a.out)
 
     log = []                 # (is_counter, fit) of every _fit_steps call
     ties = {"within": False, "across": False}
