@@ -13,8 +13,8 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_chisq.h"
-#include "fsq_glibc_pow.h"
 #include "fsq_pairwise.h"
+#include "fsq_plateau_common.h"
 
 namespace {
 
@@ -22,13 +22,6 @@ constexpr int WAVE = 64;
 constexpr int CS_UNKNOWN = -2, CS_NONE = -1;
 constexpr int MAX_BLOCKS = 8192;
 constexpr int LDS_BYTES_PER_FRAME = 4 * 8 + 7 * 2 + 1, WS_BYTES_PER_FRAME = 5 * 8 + 4;
-
-// pow(x, 2.0) as glibc, with the exp tail inlined so that the kernels make no call (a call costs a scratch frame)
-__device__ __forceinline__ double cs_pow2(double x) { return sf_pow<2, true>(x); }
-
-// No input is a NaN, so a NaN result is one an invalid operation made (0 / 0 for R^2 of a flat trace, inf / inf).  The
-// reference ran on x86-64, whose default NaN has the sign bit set; the GPU's has not.  Results are compared bit for bit.
-__device__ __forceinline__ double x86_nan(double v) { return v != v ? fsq_dbl(0xfff8000000000000ull) : v; }
 
 struct ChiCfg {
     int max_frames, Fp, num_steps, L, ignore_cf, fit_cap;
@@ -290,26 +283,7 @@ __global__ void __launch_bounds__(WAVE) kcs_split_scan(const double* __restrict_
     }
 }
 
-// ---- merge filters and R^2: one lane per trace ------------------------------------------------------------------
-// valid: 1 <= cnt <= n <= max_frames, 0 <= start_0, stop_i + 1 == start_{i+1}, start_i <= stop_i, stop_last < n
-__device__ __forceinline__ bool plateaus_valid(int n, int max_frames, int cnt, const int32_t* st, const int32_t* so)
-{
-    bool ok = n >= 1 && n <= max_frames && n <= FSQ_STEPFIT_MAX_MIRRORED && cnt >= 1 && cnt <= n && st[0] >= 0;
-    for (int i = 0; ok && i < cnt; i++) {
-        ok = st[i] <= so[i] && so[i] < n;
-        if (ok && i + 1 < cnt) ok = so[i] + 1 == st[i + 1];
-    }
-    return ok;
-}
-
-// _plateau_squared_residuals for lum[a..b] around h
-__device__ __forceinline__ double seq_residual(const double* lum, int a, int b, double h)
-{
-    double r = 0.0;
-    for (int f = a; f <= b; f++) r += cs_pow2(lum[f] - h);
-    return r;
-}
-
+// ---- merge filters and R^2: one lane per trace (plateaus_valid, seq_residual: fsq_plateau_common.h) ---------------
 __global__ void __launch_bounds__(WAVE) kcs_merge_filter(const double* __restrict__ lum_all, const int32_t* __restrict__ len,
                                                          long long n_traces, int max_frames, const int32_t* __restrict__ in_start,
                                                          const int32_t* __restrict__ in_stop, const double* __restrict__ in_h,

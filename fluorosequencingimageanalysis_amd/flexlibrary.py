@@ -1087,10 +1087,10 @@ class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
         return self.invalid_fields_mask
 
 
-from .stepfitting import PhotometryTrace, PlateauTrace  # noqa: E402  (flexlibrary.py:1595-1662; re-exported here)
+from .stepfitting import PhotometryTrace, PlateauTrace, Trace  # noqa: E402  (flexlibrary.py:1320-1662; re-exported here)
 
 
-class SimpleTrace(object):
+class SimpleTrace(Trace):
     """A Trace that is a list of Spots (or None) through frames (flexlibrary.py:1536-1593); (h, w) is that of the first
     non-None Spot."""
 
@@ -1103,6 +1103,52 @@ class SimpleTrace(object):
         else:
             raise Exception("flexlibrary.Trace.trace_hw: this Trace is composed entirely of None's.")
         self.num_frames = len(trace)
+
+    def photometry(self, frame, photometry_method='mexican_hat', **kwargs):
+        """The photometry of the Spot in frame; the int 0 where the trace has none."""
+        spot = self.trace[frame]
+        return 0 if spot is None else spot.photometry(method=photometry_method, **kwargs)
+
+    def coordinates(self, frame):
+        spot = self.trace[frame]
+        return (None, None) if spot is None else (spot.h, spot.w)
+
+    def plateau_starts(self):
+        return set(range(self.num_frames))
+
+
+def _spot_photometries(frames, traces, photometry_method, kwargs):
+    """trace.photometry(f) for every frame of every SimpleTrace / PhotometryTrace, one list per trace (the int 0 for a None Spot).
+    The mexican-hat photometries of all Spots that lie in `frames` come from one fsq_mexican_hat call."""
+    from . import photometry as _ph
+    index = {id(frame): f for f, frame in enumerate(frames or [])}
+    rows, fhw, where = [], [], []
+    batch = photometry_method == 'mexican_hat' and not set(kwargs) - {"brim_size", "radius", "return_invalid"} and \
+        kwargs.get("return_invalid", True) and kwargs.get("radius", 9) is not None
+    for t, trace in enumerate(traces):
+        if isinstance(trace, PhotometryTrace):
+            rows.append([trace.photometry(f) for f in range(trace.num_frames)])
+            continue
+        if not isinstance(trace, SimpleTrace):
+            raise NotImplementedError("spot traces must be SimpleTrace or PhotometryTrace objects")
+        row = []
+        for f, spot in enumerate(trace.trace):
+            if spot is None:
+                row.append(0)
+            elif batch and isinstance(spot, Spot) and id(spot.parent_Image) in index:
+                fhw.append((index[id(spot.parent_Image)], spot.h, spot.w))
+                where.append((t, f))
+                row.append(None)
+            else:
+                row.append(spot.photometry(method=photometry_method, **kwargs))
+        rows.append(row)
+    if fhw:
+        stack = np.stack([np.asarray(fr.image) for fr in frames])
+        phot = _ph.mexican_hat_photometry_metric(stack, np.asarray(fhw, np.int64).reshape(-1, 3), kwargs.get("brim_size", 6),
+                                                 kwargs.get("radius", 9))
+        for (t, f), v in zip(where, phot):
+            rows[t][f] = v
+    return rows
 
 
 class TimetraceExperiment(Experiment):
@@ -1182,12 +1228,139 @@ class TimetraceExperiment(Experiment):
         rows = [[0.0] * trace.num_frames for trace in traces]          # (a None Spot's photometry is 0)
         for (t, f), v in zip(where, phot.tolist()):
             rows[t][f] = v
+        # (photometry_min is accepted and not handed on: the reference's stepfit_tracks drops it on the way to
+        # Trace.stepfit_photometries, flexlibrary.py:3499-3508, and its recorded CSV shows unclamped fits - DESIGN.md 4.13)
         fits = _sf.stepfit_photometries(rows, mirror_start=mirror_start, chung_kennedy=chung_kennedy, p_threshold=p_threshold,
-                                        photometry_min=photometry_min, keys=keys)
+                                        photometry_min=None, keys=keys)
         step_fits = {}
-        for key, (ph, ck, pl, tf) in zip(keys, fits):
+        for trace, key, (ph, ck, pl, tf) in zip(traces, keys, fits):
+            if any(spot is None for spot in trace.trace):
+                # (Trace.photometries counts a None Spot as the int 0; unfiltered it reaches the CSV as '0')
+                ph.trace = tuple(0 if spot is None else v for spot, v in zip(trace.trace, ph.trace))
+                if chung_kennedy == 0:
+                    ck.trace = [0 if spot is None else v for spot, v in zip(trace.trace[trace.num_frames - len(ck.trace):], ck.trace)]
             step_fits[key] = tf
             self.step_fit_intermediates.setdefault(key, {}).update(
                 {'photometries': ph, 'ck_filtered_photometries': ck, 'plateaus': pl, 't_filtered_plateaus': tf})
         self.step_fits = step_fits
         return self.step_fits, self.step_fit_intermediates
+
+    def _get_all_intermediates(self):
+        """The set of intermediates every trace has (flexlibrary.py:3538-3548); raises unless all traces have the same."""
+        key_sets = [set(d.keys()) for d in self.step_fit_intermediates.values()]
+        first = key_sets.pop()
+        if not all(first == k for k in key_sets):
+            raise Exception("All traces must have identical intermediates.")
+        return first
+
+    def save_experiment_as_csv(self, output_path, dialect='excel', include_step_fits=False, photometry_method='mexican_hat',
+                               include_intermediates=None, **kwargs):
+        """spot_traces, step_fits and step_fit_intermediates as one CSV, a row per trace and frame (flexlibrary.py:3550-3709);
+        returns the number of rows written including the header.
+
+        All mexican-hat photometries come from one fsq_mexican_hat call, and the plateau of every frame, `Step #` and R^2 of
+        all traces from one fsq_timetrace_table call (timetrace.py); PlateauTrace intermediates are expanded
+        by fsq_plateau_values.  Everything is validated before the file is opened: where the reference raises halfway and
+        leaves a truncated file, this raises the same exception type and writes nothing.  Strings are made once per
+        plateau; floats are Python 2's str(), as pflib.save_psfs_csv writes them.  Step fits and PlateauTrace intermediates
+        must be consecutive plateaus from frame 0 (ValueError otherwise)."""
+        import csv
+        from . import timetrace as _tt
+        from .pflib import _py2_str
+        traces = list(self.spot_traces)
+        if include_intermediates is True:
+            include_intermediates = list(self._get_all_intermediates())
+        if include_intermediates is not None:
+            include_intermediates = sorted(include_intermediates)
+        header = list(_tt.HEADER) + (_tt.STEP_FIT_HEADER if include_step_fits else []) + \
+            [str(i) for i in (include_intermediates or [])]
+        inter = [self.step_fit_intermediates[(trace.h, trace.w)] for trace in traces]        # (KeyError as in the reference)
+        phot = _spot_photometries(self.frames, traces, photometry_method, kwargs)
+        fits = []
+        if include_step_fits and traces:
+            fits = [self.step_fits[(trace.h, trace.w)] for trace in traces]
+            if not all(isinstance(sf, PlateauTrace) for sf in fits):
+                raise NotImplementedError("step fits must be PlateauTrace objects")
+            table = _tt.timetrace_table(phot, [sf.trace for sf in fits])
+        columns = []                                               # per intermediate: per trace a function frame -> cell
+        for name in include_intermediates or []:
+            objs = [d[name] for d in inter]
+            plateau_like = [t for t, o in enumerate(objs) if isinstance(o, PlateauTrace)]
+            if not all(isinstance(o, (PlateauTrace, PhotometryTrace)) for o in objs):
+                raise NotImplementedError("intermediates must be PhotometryTrace or PlateauTrace objects")
+            index = {}
+            if plateau_like:
+                torch = _engine._torch()
+                for t in plateau_like:
+                    if objs[t].num_frames != traces[t].num_frames:
+                        raise ValueError("intermediate %r of trace %d does not cover the trace's frames" % (name, t))
+                mf = max(traces[t].num_frames for t in plateau_like)
+                rows = _tt.plateau_rows([objs[t].trace for t in plateau_like], mf)
+                out = _tt.plateau_values_device(*(torch.from_numpy(a).cuda() for a in rows), want_index=True)
+                status, idx = out["status"].cpu().numpy(), out["index"].cpu().numpy()
+                if status.any():
+                    raise ValueError("intermediate %r of trace %d: plateaus must be consecutive from frame 0" %
+                                     (name, plateau_like[int(np.flatnonzero(status)[0])]))
+                index = {t: idx[i] for i, t in enumerate(plateau_like)}
+            cells = []
+            for t, o in enumerate(objs):
+                if t in index:
+                    text = [_py2_str(p[2]) for p in o.trace]
+                    cells.append([text[k] for k in index[t][:traces[t].num_frames].tolist()])
+                else:
+                    text = [_py2_str(v) for v in o.trace]
+                    cells.append([text[min(f, len(text) - 1)] for f in range(traces[t].num_frames)])
+            columns.append(cells)
+        rows_written = 1
+        with open(output_path, 'w', newline='') as f:
+            wr = csv.writer(f, dialect=dialect)
+            wr.writerow(header)
+            for t, trace in enumerate(traces):
+                base = [str(t), str(trace.h), str(trace.w)]
+                n = trace.num_frames
+                if include_step_fits:
+                    heights = [_py2_str(p[2]) for p in fits[t].trace]
+                    r2 = _py2_str(float(table["r2"][t]))
+                    k_row, s_row = table["plateau_index"][t, :n].tolist(), table["step_num"][t, :n].tolist()
+                    l_row = table["plateau_length"][t, :n].tolist()
+                for fi in range(n):
+                    v = phot[t][fi]
+                    row = base + [str(fi), repr(float(v)) if isinstance(v, (float, np.floating)) else str(v)]
+                    if include_step_fits:
+                        sn = s_row[fi]
+                        row += ['None' if sn < 0 else str(sn), heights[k_row[fi]], 'None' if sn < 0 else heights[sn], str(l_row[fi]), r2]
+                    row += [cells[t][fi] for cells in columns]
+                    wr.writerow(row)
+                rows_written += n
+        return rows_written
+
+    def save_traces_pkl(self, path):
+        """self.spot_traces as a protocol-0 pickle (flexlibrary.py:3711-3713), written as the project's other pickles."""
+        from . import pflib as _pf
+        with open(path, 'wb') as f:
+            f.write(_pf._py2_pickle_bytes(self.spot_traces))
+
+    def wildcolor_plot_tracks(self, filepath_prefix, color_list=('red', 'blue', 'yellow', 'purple', 'orange', 'pink', 'lightblue',
+                                                                 'green'), num_colors=8):
+        """One PNG per frame with a square on every track's Spot, a random colour per track (flexlibrary.py:3384-3447):
+        filepath_prefix + the zero-filled frame index + '.png', through pflib.save_psfs_png.  Returns the paths."""
+        import math
+        import random
+        from . import pflib as _pf
+        saved = []
+        if self.spot_traces is None:
+            return tuple(saved)
+        colors = {t: random.choice(color_list[:num_colors]) for t, _ in enumerate(self.spot_traces)}
+        zfill = int(np.ceil(math.log(len(self.frames), 10)))
+        for f, frame in enumerate(self.frames):
+            psfs, square_colors = {}, {}
+            for t, track in enumerate(self.spot_traces):
+                h, w = track.coordinates(f)
+                if h is None or w is None:
+                    continue
+                psfs.setdefault((h, w), tuple([0] * 12))
+                square_colors.setdefault((h, w), colors[t])
+            saved.append(_pf.save_psfs_png(psfs=psfs, image_path=frame.metadata['filepath'], timestamp_epoch=None,
+                                           output_path=filepath_prefix + str(f).zfill(zfill) + '.png', square_size=9,
+                                           square_color=None, square_colors=square_colors))
+        return tuple(saved)

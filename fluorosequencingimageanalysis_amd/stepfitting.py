@@ -6,8 +6,13 @@ stepfit_records is the fast path (flat arrays, no Python object per plateau); st
 drop-ins with the reference's names and defaults.
 
 chi_squared_step_fitter, filter_upsteps, filter_small_steps and stepfit_r_squared (include/fsq_chisq.h) are drop-ins as well;
-chisq_records / chisq_device fit many traces in one launch."""
+chisq_records / chisq_device fit many traces in one launch.
+
+Trace and the plateau / step list helpers (plateau_value, plateaus_to_steps, last_step_info, frame_plateau, plateau_starts)
+are the host-side surface save_experiment_as_csv is written against; timetrace.py computes the same table for whole
+experiments on the GPU."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -20,7 +25,55 @@ CK_WINDOW_LENGTHS = (2, 4, 8, 16)     # the live path's CK windows (flexlibrary.
 LIVE_WINDOW_RADIUS = 6                 # flexlibrary.py:1439
 
 
-class PhotometryTrace(object):
+def _pow2(v):
+    """`v ** 2` of the reference's Python 2 / numpy scalars: libm's pow(v, 2.0), inf where that overflows."""
+    try:
+        return math.pow(v, 2.0)
+    except OverflowError:
+        return math.inf
+
+
+class Trace(object):
+    """flexlibrary.Trace (flexlibrary.py:1320-1514) without the step fit itself (stepfit_photometries above takes whole
+    batches): what TimetraceExperiment.save_experiment_as_csv asks of a trace.  Subclasses define photometry(frame)."""
+
+    def photometry(self, **kwargs):
+        raise AttributeError("Every Trace subclass must implement its own photometry() method")
+
+    def photometries(self, photometry_min=None, photometry_method='mexican_hat', **kwargs):
+        """The photometries of every Spot of self.trace as a tuple; a None counts the int 0; values below photometry_min
+        are raised to it."""
+        out = [spot.photometry(method=photometry_method, **kwargs) if spot is not None else 0 for spot in self.trace]
+        if photometry_min is not None:
+            out = [max(photometry_min, v) for v in out]
+        return tuple(out)
+
+    def frame_output(self, frame, **kwargs):
+        return self.photometry(frame, **kwargs)
+
+    @staticmethod
+    def trace_comparison_rss(trace_A, trace_B, photometry_method='mexican_hat', **kwargs):
+        """Left-to-right sum over the frames of (A.photometry(f) - B.photometry(f)) ** 2."""
+        if trace_A.num_frames != trace_B.num_frames:
+            raise Exception("trace_A and trace_B must cover an identical number of frames for comparison to be valid.")
+        return sum([_pow2(trace_A.photometry(frame=f, photometry_method=photometry_method, **kwargs) -
+                          trace_B.photometry(frame=f, photometry_method=photometry_method, **kwargs))
+                    for f in range(trace_A.num_frames)])
+
+    def total_sum_squares(self, photometry_method='mexican_hat', **kwargs):
+        photometries = self.photometries(photometry_min=None, photometry_method=photometry_method, **kwargs)
+        photometry_mean = float(np.mean(photometries))
+        return sum(_pow2(p - photometry_mean) for p in photometries)
+
+    @staticmethod
+    def coefficient_of_determination(trace_A, trace_B, photometry_method='mexican_hat', **kwargs):
+        """1 - rss / tss of trace_B's photometries as a fit of trace_A's (ZeroDivisionError for a constant trace_A)."""
+        rss = float(Trace.trace_comparison_rss(trace_A, trace_B, photometry_method=photometry_method, **kwargs))
+        tss = float(trace_A.total_sum_squares(photometry_method=photometry_method, **kwargs))
+        return 1.0 - rss / tss
+
+
+class PhotometryTrace(Trace):
     """flexlibrary.PhotometryTrace (flexlibrary.py:1595-1611): a sequence of photometries at (h, w)."""
 
     def __init__(self, trace, h, w):
@@ -35,7 +88,7 @@ class PhotometryTrace(object):
         return set(range(self.num_frames))
 
 
-class PlateauTrace(object):
+class PlateauTrace(Trace):
     """flexlibrary.PlateauTrace (flexlibrary.py:1630-1662): a list of (start, stop, height) plateaus at (h, w)."""
 
     def __init__(self, trace, h, w):
@@ -43,8 +96,58 @@ class PlateauTrace(object):
         self.h, self.w = h, w
         self.num_frames = trace[-1][1] + 1 if len(trace) > 0 else 0
 
+    def photometry(self, frame, **kwargs):
+        return plateau_value(self.trace, frame)
+
+    def last_step_info(self, frame):
+        """stepfitting_library.last_step_info of the PLATEAUS, as the reference calls it (flexlibrary.py:1652): in plateau
+        k >= 1 that is (k - 1, start_{k-1}, h_{k-1}), not a step's number and magnitude."""
+        return last_step_info(self.trace, frame)
+
+    def frame_plateau(self, frame):
+        return frame_plateau(self.trace, frame)
+
     def plateau_starts(self):
-        return set(p[0] for p in self.trace)
+        return plateau_starts(self.trace)
+
+
+# ---- plateau and step lists (stepfitting_library.py:508-529, :594-676, :1749) --------------------------------------------
+def plateau_value(plateaus, frame):
+    """Height of the first plateau that holds frame; ValueError when none does."""
+    for start, stop, height in plateaus:
+        if start <= frame <= stop:
+            return height
+    raise ValueError("frame " + str(frame) + " is outside of plateaus " + str(plateaus))
+
+
+def plateaus_to_steps(plateaus):
+    """[(stop_A, start_B, height_B - height_A)] for every pair of neighbouring plateaus."""
+    return [(a[1], b[0], b[2] - a[2]) for a, b in zip(plateaus[:-1], plateaus[1:])]
+
+
+def last_step_info(steps, frame):
+    """(number, pre-step frame, magnitude) of the last step (pre_frame, post_frame, magnitude) before frame: the first step
+    whose post_frame <= frame <= the next step's pre_frame, else the last step if frame >= its pre_frame, else three Nones."""
+    if frame < 0:
+        raise ValueError("frame must be a positive integer.")
+    for s in range(len(steps) - 1):
+        if steps[s][1] <= frame <= steps[s + 1][0]:
+            return s, steps[s][0], steps[s][2]
+    if len(steps) and frame >= steps[-1][0]:
+        return len(steps) - 1, steps[-1][0], steps[-1][2]
+    return None, None, None
+
+
+def frame_plateau(plateaus, frame):
+    """((start, stop, height), index) of the first plateau that holds frame, else ((None, None, None), None)."""
+    for p, (start, stop, height) in enumerate(plateaus):
+        if start <= frame <= stop:
+            return (start, stop, height), p
+    return (None, None, None), None
+
+
+def plateau_starts(plateaus):
+    return set(start for start, _stop, _height in plateaus)
 
 
 def _rows(sequences, none_is_zero, min_frames, nan_error):
