@@ -777,6 +777,80 @@ def _filtered_counts(counts, include_first_frame_only):
             if tuple(sorted(bt, reverse=True)) == bt and (include_first_frame_only or bt[1])}
 
 
+# ---- the text of the two CSV files and of the summary: shared by the classes below and by the records route (experiment.py) ----
+
+def _track_photometries_header(save_averages, n_frames):
+    if save_averages:
+        return ['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY', 'AVERAGE_INTENSITY']
+    return ['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY'] + ['FRAME ' + str(i) for i in range(n_frames)]
+
+
+def _track_photometries_row(chan, e, h, w, category, values, save_averages):
+    """One row of track_photometries_as_csv: `values` holds the trace's photometry per frame, None where it has no Spot."""
+    if save_averages:
+        mean = np.mean([v for v in values if v is not None])
+        return [str(chan), str(e), str(h), str(w), str(category), str(mean)]
+    return [str(chan), str(e), str(h), str(w), str(category)] + [str(v) if v is not None else '0' for v in values]
+
+
+def _write_category_counts_csv(filepath, to_save, collate_fields, dialect='excel'):
+    """{channel: {field: {pattern: count}}} as category_counts_as_csv writes it (flexlibrary.py:2948-3024)."""
+    import csv
+    channels = sorted(to_save.keys())            # (filtered=False: a tuple has no keys - the reference fails the same way)
+    patterns = sorted(set(pattern for fields in to_save.values() for counts in fields.values() for pattern in counts))
+    with open(filepath, 'w') as output_file:
+        writer = csv.writer(output_file, dialect=dialect)
+        writer.writerow(["Pattern", "Field", "Channel", "Count"] if collate_fields else ["Pattern", "Channel", "Count"])
+        for pattern in patterns:
+            onoff = Experiment.truefalse_to_onoff(pattern)
+            for chan in channels:
+                if collate_fields:
+                    for e, ex in to_save[chan].items():
+                        writer.writerow([onoff, str(e), str(chan), str(ex[pattern]) if pattern in ex else '0'])
+                else:
+                    writer.writerow([onoff, str(chan), str(sum(ex[pattern] for ex in to_save[chan].values() if pattern in ex))])
+    return filepath
+
+
+def _category_counts_string(to_string, collate_fields):
+    """{channel: {field: {pattern: count}}} as the text of category_counts_as_string (flexlibrary.py:3026-3077)."""
+    out = ''
+    for chan, ex in sorted(to_string.items(), key=lambda x: x[0]):
+        if collate_fields:
+            for e, patterns in ex.items():
+                out += " Channel " + str(chan) + " Frame " + str(e) + "\n"
+                for pattern, count in sorted(patterns.items(), key=lambda x: x[0]):
+                    out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
+        else:
+            merged = {}
+            for patterns in ex.values():
+                for pattern, count in patterns.items():
+                    merged[pattern] = merged.get(pattern, 0) + count
+            out += str(chan) + "\n"
+            for pattern, count in sorted(merged.items(), key=lambda x: x[0]):
+                out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
+    return out
+
+
+def _offsets_string(by_frame):
+    """{frame: {field: {channel: (d_h, d_w)}}} as the text of offsets_as_string."""
+    out = ''
+    for f, frame_offsets in sorted(by_frame.items()):
+        out += "Frame " + str(f) + "\n"
+        for e, ex_offsets in sorted(frame_offsets.items(), key=lambda x: x[0]):
+            out += "    Field " + str(e) + "\n"
+            for c, (h, w) in sorted(ex_offsets.items(), key=lambda x: x[0]):
+                out += "        Channel " + str(c) + " " + str((h, w)) + "\n"
+            all_h, all_w = [h for h, w in ex_offsets.values()], [w for h, w in ex_offsets.values()]
+            out += "        Mean Offsets for Field " + str(e) + " = " + str((np.mean(all_h), np.mean(all_w))) + "\n"
+            out += "        Std.Dev. Offsets for Field " + str(e) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
+        all_h = [h for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
+        all_w = [w for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
+        out += "    Mean Offsets for Frame " + str(f) + str((np.mean(all_h), np.mean(all_w))) + "\n"
+        out += "        Std.Dev. Offsets for Field " + str(f) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
+    return out
+
+
 class MultifieldSequenceExperiment(Experiment):
     """SequenceExperiments over several fields (flexlibrary.py:2384-2468).  As in the reference, the class only serves as
     the base of MultifieldMultichannelSequenceExperiment: its own constructor raises DeprecationWarning."""
@@ -928,11 +1002,8 @@ class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
         rows = 0
         with open(filepath, 'w') as output_file:
             writer = csv.writer(output_file, dialect=dialect)
-            if save_averages:
-                writer.writerow(['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY', 'AVERAGE_INTENSITY'])
-            else:
-                n_frames = len(list(self.experimental_fields[0].channels.values())[0].peptide_frames)
-                writer.writerow(['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY'] + ['FRAME ' + str(i) for i in range(n_frames)])
+            n_frames = None if save_averages else len(list(self.experimental_fields[0].channels.values())[0].peptide_frames)
+            writer.writerow(_track_photometries_header(save_averages, n_frames))
             for chan, categories in btcp.items():
                 for e, ex in categories.items():
                     for category, trace_photometries in ex.items():
@@ -940,12 +1011,8 @@ class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
                             # (the placeholder is told by identity, as the reference does: an adjustment_function builds new
                             #  tuples, and then the first frame's entry is taken whatever it holds, flexlibrary.py:2872-2874)
                             h, w = [fp[:2] for fp in photometry if fp is not _NONE3][0]
-                            if save_averages:
-                                mean = np.mean([fp[2] for fp in photometry if fp[2] is not None])
-                                writer.writerow([str(chan), str(e), str(h), str(w), str(category), str(mean)])
-                            else:
-                                writer.writerow([str(chan), str(e), str(h), str(w), str(category)] +
-                                                [str(fp[2]) if fp[2] is not None else '0' for fp in photometry])
+                            writer.writerow(_track_photometries_row(chan, e, h, w, category, [fp[2] for fp in photometry],
+                                                                    save_averages))
                             rows += 1
         return rows
 
@@ -964,47 +1031,18 @@ class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
                                ignore_invalid_fields=False):
         """Pattern, (Field,) Channel, Count rows of filtered_binary_trace_category_counts; patterns and channels sorted,
         fields summed unless collate_fields.  Returns filepath.  flexlibrary.py:2948-3024."""
-        import csv
         if filtered:
             to_save = self.filtered_binary_trace_category_counts(ignore_invalid_fields=ignore_invalid_fields)
         else:
             to_save = self.count_binary_trace_categories(ignore_invalid_fields=ignore_invalid_fields)
-        channels = sorted(to_save.keys())            # (filtered=False: a tuple has no keys - the reference fails the same way)
-        patterns = sorted(set(pattern for fields in to_save.values() for counts in fields.values() for pattern in counts))
-        with open(filepath, 'w') as output_file:
-            writer = csv.writer(output_file, dialect=dialect)
-            writer.writerow(["Pattern", "Field", "Channel", "Count"] if collate_fields else ["Pattern", "Channel", "Count"])
-            for pattern in patterns:
-                onoff = Experiment.truefalse_to_onoff(pattern)
-                for chan in channels:
-                    if collate_fields:
-                        for e, ex in to_save[chan].items():
-                            writer.writerow([onoff, str(e), str(chan), str(ex[pattern]) if pattern in ex else '0'])
-                    else:
-                        writer.writerow([onoff, str(chan), str(sum(ex[pattern] for ex in to_save[chan].values() if pattern in ex))])
-        return filepath
+        return _write_category_counts_csv(filepath, to_save, collate_fields, dialect)
 
     def category_counts_as_string(self, filtered=True, collate_fields=False, ignore_invalid_fields=False):
         """The filtered counts as a multi-line string.  flexlibrary.py:3026-3077."""
         if not filtered:
             raise NotImplementedError("filtered=False not yet implemented.")
         to_string = self.filtered_binary_trace_category_counts(ignore_invalid_fields=ignore_invalid_fields)
-        out = ''
-        for chan, ex in sorted(to_string.items(), key=lambda x: x[0]):
-            if collate_fields:
-                for e, patterns in ex.items():
-                    out += " Channel " + str(chan) + " Frame " + str(e) + "\n"
-                    for pattern, count in sorted(patterns.items(), key=lambda x: x[0]):
-                        out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
-            else:
-                merged = {}
-                for patterns in ex.values():
-                    for pattern, count in patterns.items():
-                        merged[pattern] = merged.get(pattern, 0) + count
-                out += str(chan) + "\n"
-                for pattern, count in sorted(merged.items(), key=lambda x: x[0]):
-                    out += "    " + Experiment.truefalse_to_onoff(pattern) + "    " + str(count) + "\n"
-        return out
+        return _category_counts_string(to_string, collate_fields)
 
     def _summed(self, name, ignore_invalid_fields):
         count = {}
@@ -1047,21 +1085,8 @@ class MultifieldMultichannelSequenceExperiment(MultifieldSequenceExperiment):
     def offsets_as_string(self, ignore_invalid_fields=False):
         """get_offsets_by_frame as text, with mean and standard deviation per field and per frame.  flexlibrary.py:3168-3201
         (the labels of the per-frame lines are the reference's)."""
-        out = ''
-        for f, frame_offsets in sorted(self.get_offsets_by_frame(ignore_invalid_fields=ignore_invalid_fields).items()):
-            out += "Frame " + str(f) + "\n"
-            for e, ex_offsets in sorted(frame_offsets.items(), key=lambda x: x[0]):
-                out += "    Field " + str(e) + "\n"
-                for c, (h, w) in sorted(ex_offsets.items(), key=lambda x: x[0]):
-                    out += "        Channel " + str(c) + " " + str((h, w)) + "\n"
-                all_h, all_w = [h for h, w in ex_offsets.values()], [w for h, w in ex_offsets.values()]
-                out += "        Mean Offsets for Field " + str(e) + " = " + str((np.mean(all_h), np.mean(all_w))) + "\n"
-                out += "        Std.Dev. Offsets for Field " + str(e) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
-            all_h = [h for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
-            all_w = [w for ex_offsets in frame_offsets.values() for h, w in ex_offsets.values()]
-            out += "    Mean Offsets for Frame " + str(f) + str((np.mean(all_h), np.mean(all_w))) + "\n"
-            out += "        Std.Dev. Offsets for Field " + str(f) + " = " + str((np.std(all_h), np.std(all_w))) + "\n"
-        return out
+        return _offsets_string(self.get_offsets_by_frame(ignore_invalid_fields=ignore_invalid_fields))
+
 
     def discard_invalid_traces(self, ignore_invalid_fields=False, **pparams):
         seqs = self._sequences(ignore_invalid_fields)
