@@ -1,0 +1,115 @@
+"""Fit track photometries using the lognormal algorithm: the reference's lognormal_fitter_v2.py command line, with the
+fit on the GPU.
+
+  python -m fluorosequencingimageanalysis_amd.lognormal_fitter_v2 TRACKS.csv [-c -w -m -o -e -s -n --max_possible
+      --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate]
+
+Steps as there: alpha from the histogram of all photometries, the alpha-adjusted and the truncated dicts, a first beta from
+the last ON frames, a first fit, the ON/OFF adjustment per (cycle, field), a second beta and the second fit.  Written next to
+TRACKS.csv under the reference's names (TRACKS.csv_<hash>_ch<c>_...): COMMANDLINE.pkl, INTERMEDIATES_v2.pkl, CLUSTERED.csv
+(empty), SIGNALS.pkl and RAW_PHOTOMETRIES.pkl, pickles in protocol 0.  The three plotly HTML files are not built.
+--max_deviation is parsed and, as in the reference, 3 is what the fit gets; -n is accepted and unused."""
+import argparse
+import sys
+import time
+from os.path import abspath
+
+from . import lognormal as _ln
+from .pflib import _epoch_to_hash, _py2_pickle_bytes, _py2_round
+
+
+class _Formatter(argparse.ArgumentDefaultsHelpFormatter, argparse.RawDescriptionHelpFormatter):
+    pass
+
+
+def make_parser():
+    p = argparse.ArgumentParser(prog="lognormal_fitter_v2", description=__doc__, formatter_class=_Formatter)
+    p.add_argument('tracks', nargs=1, type=str, help="track_photometries_??????.csv file to fit.")
+    p.add_argument('-c', '--channel', type=int, default=1, help="Which channel to fit. Must be either 1 or 2.")
+    p.add_argument('-w', '--wavelength', type=int, default=0, help="Wavelength of the channel (heatmaps only: unused).")
+    p.add_argument('-m', '--num_mocks', type=int, default=4, help="Number of mocks performed (heatmaps only: unused).")
+    p.add_argument('-o', '--num_mocks_omitted', type=int, default=1, help="Number of mocks not imaged (heatmaps only: unused).")
+    p.add_argument('-e', '--num_edmans', type=int, default=8, help="Number of Edmans performed (heatmaps only: unused).")
+    p.add_argument('-s', '--sequence', type=str, default=None, help="Peptide sequence as string (heatmaps only: unused).")
+    p.add_argument('-n', '--num_processors', type=int, default=None, help="Accepted and unused: the fit is one GPU launch.")
+    p.add_argument('--max_possible', type=int, default=5, help="Maximum number of fluors to try to fit.")
+    p.add_argument('--max_deviation', type=int, default=3,
+                   help="Maximum standard deviations away from mean for fitting an intensity to a fluor (parsed; the fit gets 3).")
+    p.add_argument('--ddif', type=float, default=0.30, help="Dye-dye interaction factor.")
+    p.add_argument('--beta_sigma', type=float, default=0.20, help="Lognormal shape parameter.")
+    p.add_argument('--beta', type=float, default=None, help="Manually specify 1-fluor intensity")
+    p.add_argument('--no_adjustment', action='store_true', default=False,
+                   help="Do not perform ON->OFF based per-image photometry adjustment.")
+    p.add_argument('--no_multidrop', action='store_true', default=False, help="No drops greater than one dye allowed during fit.")
+    p.add_argument('--truncate', type=int, default=0,
+                   help="Ignore this number of cycles at the beginning when trying to guess the one fluor intensity.")
+    return p
+
+
+def _dump(obj, path):
+    with open(path, 'wb') as f:
+        f.write(_py2_pickle_bytes(obj))
+
+
+def main(argv=None, timestamp_epoch=None, device=None):
+    """Runs the chain; returns a dict of everything it computed (alpha, betas, both fits, the output paths)."""
+    argv = list(sys.argv if argv is None else argv)
+    args = make_parser().parse_args(argv[1:])
+    tracks_filepath = abspath(args.tracks[0])
+    channel = 'ch' + str(args.channel)
+    if timestamp_epoch is None:
+        timestamp_epoch = _py2_round(time.time())
+    timestamp_hash = _epoch_to_hash(timestamp_epoch)
+    base = tracks_filepath + "_" + str(timestamp_hash) + "_" + str(channel) + "_"
+    print("Using timestamp_hash " + str(timestamp_hash))
+    _dump(argv, base + 'COMMANDLINE.pkl')
+
+    photometries, row_photometries = _ln.read_track_photometries_csv(tracks_filepath, head_truncate=0, tail_truncate=0,
+                                                                     downstep_filtered=True, channels=[channel])
+    tracks = list(_ln.unwind_photometries(photometries))
+    raw_photometries = tuple([i for t in tracks for i in t[5]])
+    alpha = _ln._get_m0Dm1(raw_photometries=raw_photometries, optimal_bin_number=None)[7]
+    alpha_adjusted, truncated = {}, {}
+    for ch, field, h, w, category, intensities, row in tracks:
+        (alpha_adjusted.setdefault(ch, {}).setdefault(field, {})
+         .setdefault((h, w), (category, tuple([i - alpha for i in intensities]), row)))
+        # (as in the reference, the truncated dict holds the raw intensities, not the alpha-adjusted ones)
+        truncated.setdefault(ch, {}).setdefault(field, {}).setdefault((h, w), (category[args.truncate:], intensities[args.truncate:], row))
+    original_beta, original_beta_sigma = _ln.last_drop_method_v2(photometries=truncated)
+    if args.beta is not None:
+        original_beta = args.beta
+    ddif = tuple([0.0] + [args.ddif] * (args.max_possible + 1))
+    fit_kw = dict(beta_sigma=args.beta_sigma, max_possible=args.max_possible, allow_upsteps=False,
+                  allow_multidrop=not args.no_multidrop, max_deviation=3, quench_factor=0, quench_factors=ddif, device=device)
+    original_plf_results = _ln.photometries_lognormal_fit(photometries=alpha_adjusted, beta=original_beta, **fit_kw)
+    on_offs = _ln.grab_ON_OFFS(original_plf_results[3], alpha_adjust=0)
+    if not args.no_adjustment:
+        adj_photometries = _ln.ON_OFF_adjust_photometries(photometries=photometries, ON_OFFS=on_offs, alpha=alpha)
+    else:
+        adj_photometries = alpha_adjusted
+    adj_beta, adj_beta_sigma = _ln.last_drop_method_v2(photometries=adj_photometries)
+    if args.beta is not None:
+        adj_beta = args.beta
+    plf_results = (signals, total_count, none_count, all_fit_info) = \
+        _ln.photometries_lognormal_fit(photometries=adj_photometries, beta=adj_beta, **fit_kw)
+
+    _dump(((alpha, adj_beta, args.beta_sigma, ddif), plf_results, args), base + 'INTERMEDIATES_v2.pkl')
+    open(base + 'CLUSTERED.csv', 'w').close()
+    _dump(signals, base + 'SIGNALS.pkl')
+    print("")
+    print("Signals:")
+    for (signal, is_zero, s_i), count in sorted(signals.items(), key=lambda x: x[0]):
+        print(str((signal, is_zero, s_i)) + "    " + str(count))
+    print("Total number of signals: " + str(sum(signals.values())))
+    print("Total number of signals that fall to 0: " + str(sum([count for (s, z, si), count in signals.items() if z])))
+    print("")
+    _dump(raw_photometries, base + 'RAW_PHOTOMETRIES.pkl')
+    for what in ("histogram", "single drops heatmap", "double drops heatmap"):
+        print("Error saving " + what + " using plotting.py functions. Exception: the plotly HTML files are not built here")
+    return dict(alpha=alpha, original_beta=original_beta, original_beta_sigma=original_beta_sigma, adj_beta=adj_beta,
+                adj_beta_sigma=adj_beta_sigma, on_offs=on_offs, adj_photometries=adj_photometries,
+                original_plf_results=original_plf_results, plf_results=plf_results, output_filepath_base=base, args=args)
+
+
+if __name__ == "__main__":
+    main()
