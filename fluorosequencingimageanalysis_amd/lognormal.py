@@ -3,14 +3,22 @@
 The fit itself - MCsimlib._intensities_to_signal_lognormal_v8 (:5387-5493), the most expensive per-track step of the chain -
 runs on the device, one wavefront per track and one launch for a whole experiment (`lognormal_device`, `lognormal_records`,
 `photometries_lognormal_fit`; include/fsq_lognormal.h).  The host pieces of the chain (the CSV reader, the histogram bin
-search, alpha, beta, the ON/OFF adjustment) are restated here with the reference's own numpy calls.
+search, alpha, beta, the ON/OFF adjustment) are restated here with the reference's own numpy calls.  The bin search, 9 991
+histograms of all photometries for alpha alone, also runs on the device with numpy's bits (`histogram_costs_device`,
+`bin_search_records`, `histogram_counts`; include/fsq_binsearch.h): `optimal_bin_size`, `optimal_bin_count`, `_get_m0Dm1` and
+`last_drop_method_v2` take it with `device=...` and stay on the host with `device=None`.
 
 Limits of the device fit, each raised on the host before anything is launched: 1 .. 64 frames per track
 (NotImplementedError above 64, ValueError for none), max_possible in 1 .. 15 (NotImplementedError above), beta_sigma finite
 and > 0, max_deviation not NaN, finite intensities and finite log_fluor_means (ValueError); allow_upsteps=True is not built
 (NotImplementedError; the command line never passes it).  A track with more surviving sequences than `budget` (default 2^22)
 is not enumerated: it comes back with STATUS_OVER_BUDGET from the array interfaces and raises NotImplementedError naming the
-track from the dict interfaces."""
+track from the dict interfaces.
+
+Limits of the device bin search, each raised as ValueError on the host before anything is launched: at least one value, finite
+values, integers of magnitude at most 2^53 (beyond it float64 does not hold them), bin counts in 1 .. 10 000
+(FSQ_BINSEARCH_MAX_BINS), fewer than 2^31 values.  Where all values are equal the search runs on the host whatever `device` is,
+and ends as it ends there."""
 import ctypes
 import math
 from math import log, sqrt
@@ -18,12 +26,14 @@ from math import log, sqrt
 import numpy as np
 
 from . import _native as N
+from . import _native_binsearch as NB
 from . import _native_lognormal as NL
 from . import engine as _engine
 from .pflib import _py2_round
 
 STATUS_FOUND, STATUS_NONE, STATUS_OVER_BUDGET = NL.STATUS_FOUND, NL.STATUS_NONE, NL.STATUS_OVER_BUDGET
 DEFAULT_BUDGET = NL.DEFAULT_BUDGET
+MAX_BINS = NB.MAX_BINS
 
 
 # ---- the device fit ----
@@ -188,6 +198,125 @@ def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_
     return host
 
 
+# ---- the histogram bin search on the device ----
+
+def _checked_bin_counts(bin_counts):
+    """int32 bin counts after the checks the module docstring names."""
+    b = np.asarray(bin_counts)
+    if b.ndim != 1 or b.size == 0 or b.dtype.kind not in "iu":
+        raise ValueError("bin counts: a non-empty 1-D array of integers is needed")
+    if int(b.min()) < 1 or int(b.max()) > MAX_BINS:
+        raise ValueError("bin counts must be in 1 .. %d" % MAX_BINS)
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
+def _checked_values(values):
+    """float64 values after the checks the module docstring names."""
+    a = np.asarray(values).reshape(-1)
+    if a.size == 0:
+        raise ValueError("at least one value is needed")
+    if a.dtype.kind in "iub":
+        if int(a.min()) < -(1 << 53) or int(a.max()) > (1 << 53):
+            raise ValueError("integers are limited to a magnitude of 2^53")
+    elif a.dtype.kind != "f":
+        raise ValueError("finite real values are needed (integers of a magnitude of at most 2^53)")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("values must be finite")
+    return a
+
+
+def _sorted(d_values):
+    torch = _engine._torch()
+    if not d_values.is_cuda or d_values.dtype != torch.float64 or d_values.dim() != 1:
+        raise ValueError("a 1-D float64 CUDA tensor is needed")
+    if d_values.numel() < 1:
+        raise ValueError("at least one value is needed")
+    return torch.sort(d_values).values.contiguous()
+
+
+def histogram_costs_device(d_values, bin_counts, lo=None, hi=None):
+    """fsq_histogram_costs on a 1-D float64 CUDA tensor of values in any order: Shimazaki & Shinomoto's cost of every bin
+    count, as optimal_bin_size computes it, a float64 CUDA tensor.  bin_counts: integers on the host (checked here), or an
+    int32 CUDA tensor (not checked: a count outside 1 .. 10 000 comes back as NaN).  The values are sorted with torch.sort.
+    Enqueued on the current stream; nothing is read back and the result is not synchronised.
+
+    Without lo and hi the kernel takes the least and the greatest value from the sorted data (fsq_histogram_costs_sorted);
+    the host cannot see the values then, so non-finite or all-equal values give NaN in every cost instead of an error.  With
+    lo and hi (both) the caller vouches that they are the least and the greatest of finite values; bounds that cannot be
+    (hi <= lo, non-finite) raise ValueError."""
+    torch = _engine._torch()
+    if (lo is None) != (hi is None):
+        raise ValueError("lo and hi are given together or not at all")
+    d_sorted = _sorted(d_values)
+    dev = d_sorted.device
+    if torch.is_tensor(bin_counts):
+        if bin_counts.dtype != torch.int32 or bin_counts.dim() != 1 or bin_counts.device != dev:
+            raise ValueError("bin counts: a 1-D int32 tensor on the values' device is needed")
+        d_counts = bin_counts.contiguous()
+    else:
+        d_counts = torch.from_numpy(_checked_bin_counts(bin_counts)).to(dev)
+    d_cost = torch.empty(int(d_counts.numel()), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if lo is None:
+            rc = NB.lib().fsq_histogram_costs_sorted(d_sorted.data_ptr(), int(d_sorted.numel()), d_counts.data_ptr(),
+                                                     int(d_counts.numel()), d_cost.data_ptr(), stream)
+        else:
+            rc = NB.lib().fsq_histogram_costs(d_sorted.data_ptr(), int(d_sorted.numel()), float(lo), float(hi), d_counts.data_ptr(),
+                                              int(d_counts.numel()), d_cost.data_ptr(), stream)
+    N.check(rc, "fsq_histogram_costs")
+    return d_cost
+
+
+def histogram_counts_device(d_values, n_bins, lo=None, hi=None):
+    """fsq_histogram_counts: np.histogram(values, bins=np.linspace(lo, hi, n_bins + 1))[0] as an int64 CUDA tensor, enqueued
+    on the current stream.  lo and hi are the least and the greatest value; where they are not given they are read back from
+    the device (one small synchronising copy).  Bounds that cannot be (equal, non-finite) raise ValueError."""
+    torch = _engine._torch()
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= MAX_BINS:
+        raise ValueError("bin counts must be in 1 .. %d" % MAX_BINS)
+    d_sorted = _sorted(d_values)
+    if lo is None or hi is None:
+        lo, hi = d_sorted[[0, -1]].tolist()
+    lo, hi = float(lo), float(hi)
+    dev = d_sorted.device
+    d_hist = torch.empty(n_bins, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = NB.lib().fsq_histogram_counts(d_sorted.data_ptr(), int(d_sorted.numel()), lo, hi, n_bins, d_hist.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "fsq_histogram_counts")
+    return d_hist
+
+
+def histogram_costs(values, bin_counts, device=None):
+    """histogram_costs_device for host values: the costs as a float64 array."""
+    a, b = _checked_values(values), _checked_bin_counts(bin_counts)
+    torch = _engine._torch()
+    d_values = torch.from_numpy(a).to(torch.device(device or "cuda"))
+    return histogram_costs_device(d_values, b, float(a.min()), float(a.max())).cpu().numpy()
+
+
+def bin_search_records(values, min_n_bins, max_n_bins, device=None):
+    """The search of optimal_bin_size over min_n_bins .. max_n_bins on the device, as a dict of NumPy values: cost (float64,
+    one per bin count), n_bins (the first bin count of least cost, optimal_bin_count's rule), lo and hi."""
+    a = _checked_values(values)
+    cost = histogram_costs(a, np.arange(int(min_n_bins), int(max_n_bins) + 1), device)
+    where = np.where(cost == np.amin(cost))
+    return {"cost": cost, "n_bins": np.int64(int(where[0][0]) + int(min_n_bins)), "lo": np.float64(a.min()), "hi": np.float64(a.max())}
+
+
+def histogram_counts(values, n_bins, device=None):
+    """np.histogram(values, bins=np.linspace(min, max, n_bins + 1))[0] on the device: an int64 array."""
+    a = _checked_values(values)
+    if not 1 <= int(n_bins) <= MAX_BINS:
+        raise ValueError("bin counts must be in 1 .. %d" % MAX_BINS)
+    torch = _engine._torch()
+    d_values = torch.from_numpy(a).to(torch.device(device or "cuda"))
+    return histogram_counts_device(d_values, n_bins, float(a.min()), float(a.max())).cpu().numpy()
+
+
 # ---- the reference's call surface ----
 
 def _signal(best_seq):
@@ -336,11 +465,18 @@ def photometries_from_records(records, channel, downstep_filtered=True, channels
     return d
 
 
-def optimal_bin_size(raw_photometries, bin_array=None):
-    """MCsimlib.optimal_bin_size (:3888-3909), Shimazaki & Shinomoto's histogram cost: (min_cost, where, cost_array)."""
+def optimal_bin_size(raw_photometries, bin_array=None, device=None):
+    """MCsimlib.optimal_bin_size (:3888-3909), Shimazaki & Shinomoto's histogram cost: (min_cost, where, cost_array).  With a
+    `device` the costs are computed there, bit for bit the same."""
     lo, hi = min(raw_photometries), max(raw_photometries)
     if bin_array is None:
         bin_array = np.array(range(10, 101))
+    if device is not None:
+        values = _checked_values(raw_photometries)
+        if values.min() != values.max():                           # (all equal: the host route, to end as it always has)
+            cost_array = histogram_costs(values, bin_array, device).reshape(-1, 1)
+            min_cost = np.amin(cost_array)
+            return min_cost, np.where(cost_array == min_cost), cost_array
     bin_size_vector = float(hi - lo) / bin_array
     cost_array = np.zeros(shape=(bin_size_vector.size, 1))
     for i, bin_size in enumerate(bin_size_vector):
@@ -350,17 +486,18 @@ def optimal_bin_size(raw_photometries, bin_array=None):
     return min_cost, np.where(cost_array == min_cost), cost_array
 
 
-def optimal_bin_count(raw_photometries, min_n_bins=10, max_n_bins=1000):
+def optimal_bin_count(raw_photometries, min_n_bins=10, max_n_bins=1000, device=None):
     """The bin count optimal_bin_size_MP (:3912-3939) settles on, searched in this process: the first bin count with the
     least cost.  (The reference splits the range over its workers and takes the first share with the least cost; it raises
     TypeError where two bin counts of one share tie.)"""
-    _, where, _ = optimal_bin_size(raw_photometries, np.array(range(min_n_bins, max_n_bins + 1)))
+    _, where, _ = optimal_bin_size(raw_photometries, np.array(range(min_n_bins, max_n_bins + 1)), device=device)
     return int(where[0][0]) + min_n_bins
 
 
-def _get_m0Dm1(raw_photometries, optimal_bin_number=None):
-    """MCsimlib._get_m0Dm1 (:3942-3979): the two highest histogram peaks and the valley between them; [7] is alpha."""
-    n_bins = optimal_bin_count(raw_photometries, 10, 10000) if optimal_bin_number is None else optimal_bin_number
+def _get_m0Dm1(raw_photometries, optimal_bin_number=None, device=None):
+    """MCsimlib._get_m0Dm1 (:3942-3979): the two highest histogram peaks and the valley between them; [7] is alpha.  `device`:
+    where the bin search runs (None: on the host)."""
+    n_bins = optimal_bin_count(raw_photometries, 10, 10000, device=device) if optimal_bin_number is None else optimal_bin_number
     hist, bins = np.histogram(a=raw_photometries, bins=n_bins)
     depth_array = np.zeros_like(hist)
     for (gi,), gv in np.ndenumerate(hist):
@@ -383,13 +520,14 @@ def _pairwise(seq):
     return zip(seq[:-1], seq[1:])
 
 
-def last_drop_method_v2(photometries):
-    """MCsimlib.last_drop_method_v2 (:5357-5384): (beta, beta_sigma) from the histogram of log(intensity) at every last ON frame."""
+def last_drop_method_v2(photometries, device=None):
+    """MCsimlib.last_drop_method_v2 (:5357-5384): (beta, beta_sigma) from the histogram of log(intensity) at every last ON frame.
+    `device`: where the bin search runs (None: on the host)."""
     if len(photometries) > 1:
         raise NotImplementedError("Currently puts all photometries together, can't handle multiple channels at once.")
     last_drop_list = [log(iON) for _, _, _, _, category, intensities, _ in unwind_photometries(photometries)
                       for i, (iON, iOFF) in enumerate(_pairwise(intensities)) if category[i] and not category[i + 1] and iON > 0]
-    obn = optimal_bin_count(last_drop_list)
+    obn = optimal_bin_count(last_drop_list, device=device)
     hist, bins = np.histogram(a=last_drop_list, bins=obn)
     hist_max, hist_argmax = np.amax(hist), np.argmax(hist)
     if hist_argmax < len(bins) - 1:

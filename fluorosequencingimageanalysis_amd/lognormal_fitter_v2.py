@@ -2,13 +2,15 @@
 fit on the GPU.
 
   python -m fluorosequencingimageanalysis_amd.lognormal_fitter_v2 TRACKS.csv [-c -w -m -o -e -s -n --max_possible
-      --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate]
+      --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate --host_bin_search]
 
 Steps as there: alpha from the histogram of all photometries, the alpha-adjusted and the truncated dicts, a first beta from
 the last ON frames, a first fit, the ON/OFF adjustment per (cycle, field), a second beta and the second fit.  Written next to
 TRACKS.csv under the reference's names (TRACKS.csv_<hash>_ch<c>_...): COMMANDLINE.pkl, INTERMEDIATES_v2.pkl, CLUSTERED.csv
 (empty), SIGNALS.pkl and RAW_PHOTOMETRIES.pkl, pickles in protocol 0.  The three plotly HTML files are not built.
---max_deviation is parsed and, as in the reference, 3 is what the fit gets; -n is accepted and unused."""
+--max_deviation is parsed and, as in the reference, 3 is what the fit gets; -n is accepted and unused.  The histogram bin
+searches behind alpha and both betas run on the GPU where there is one (include/fsq_binsearch.h) and with numpy on the host
+otherwise or with --host_bin_search; the files and the printed text are the same either way."""
 import argparse
 import sys
 import time
@@ -43,7 +45,19 @@ def make_parser():
     p.add_argument('--no_multidrop', action='store_true', default=False, help="No drops greater than one dye allowed during fit.")
     p.add_argument('--truncate', type=int, default=0,
                    help="Ignore this number of cycles at the beginning when trying to guess the one fluor intensity.")
+    p.add_argument('--host_bin_search', action='store_true', default=False,
+                   help="Run the histogram bin searches with numpy on the host, not on the GPU.")
     return p
+
+
+def _search_device(args, device):
+    """Where the bin searches run: None (the host) with --host_bin_search or without a GPU, else `device` or the current GPU."""
+    if args.host_bin_search:
+        return None
+    if device is not None:
+        return device
+    import torch
+    return "cuda" if torch.cuda.is_available() else None
 
 
 def _dump(obj, path):
@@ -68,14 +82,15 @@ def main(argv=None, timestamp_epoch=None, device=None):
                                                                      downstep_filtered=True, channels=[channel])
     tracks = list(_ln.unwind_photometries(photometries))
     raw_photometries = tuple([i for t in tracks for i in t[5]])
-    alpha = _ln._get_m0Dm1(raw_photometries=raw_photometries, optimal_bin_number=None)[7]
+    search_device = _search_device(args, device)
+    alpha = _ln._get_m0Dm1(raw_photometries=raw_photometries, optimal_bin_number=None, device=search_device)[7]
     alpha_adjusted, truncated = {}, {}
     for ch, field, h, w, category, intensities, row in tracks:
         (alpha_adjusted.setdefault(ch, {}).setdefault(field, {})
          .setdefault((h, w), (category, tuple([i - alpha for i in intensities]), row)))
         # (as in the reference, the truncated dict holds the raw intensities, not the alpha-adjusted ones)
         truncated.setdefault(ch, {}).setdefault(field, {}).setdefault((h, w), (category[args.truncate:], intensities[args.truncate:], row))
-    original_beta, original_beta_sigma = _ln.last_drop_method_v2(photometries=truncated)
+    original_beta, original_beta_sigma = _ln.last_drop_method_v2(photometries=truncated, device=search_device)
     if args.beta is not None:
         original_beta = args.beta
     ddif = tuple([0.0] + [args.ddif] * (args.max_possible + 1))
@@ -87,7 +102,7 @@ def main(argv=None, timestamp_epoch=None, device=None):
         adj_photometries = _ln.ON_OFF_adjust_photometries(photometries=photometries, ON_OFFS=on_offs, alpha=alpha)
     else:
         adj_photometries = alpha_adjusted
-    adj_beta, adj_beta_sigma = _ln.last_drop_method_v2(photometries=adj_photometries)
+    adj_beta, adj_beta_sigma = _ln.last_drop_method_v2(photometries=adj_photometries, device=search_device)
     if args.beta is not None:
         adj_beta = args.beta
     plf_results = (signals, total_count, none_count, all_fit_info) = \

@@ -1,0 +1,265 @@
+"""Histogram bin search of the lognormal chain, host side: the fixture against the Python restatement of the contract
+(include/fsq_binsearch.h), the C ABI declarations, every refusal made before a launch, the unchanged host route, and the
+command line with both routes (the device's costs stood in for by the recorded ones; no GPU needed)."""
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _binsearch_reference as B
+import _lognormal_reference as R
+from _binsearch_cases import (FIXED_BIN_COUNTS, SEEDED_SIZES, cases, golden, non_vacuity_counts, raw_of, same_files_but_for_the_flag,
+                              searches, value_sets)
+from _lognormal_cases import chain_csv_text, check_fit_against_record, restated_records
+from _lognormal_cases import golden as chain_golden
+from _util import ROOT, _bits
+
+
+def test_fixture_is_not_vacuous():
+    sets, cs = value_sets(), cases()
+    fused, le, chunk, product = non_vacuity_counts(cs, sets, searches())
+    assert fused >= 20 and le >= 20 and chunk >= 5 and product >= 5, (fused, le, chunk, product)
+    by_set = {}
+    for c in cs:
+        by_set.setdefault(sets[c["set"]]["name"], []).append(c["nb"])
+    for kind in ("int", "log"):
+        for n in SEEDED_SIZES:
+            s = next(s for s in sets if s["name"] == "%s_%d" % (kind, n))
+            assert len(s["values"]) == n and s["is_int"] == (kind == "int") and by_set[s["name"]][:len(FIXED_BIN_COUNTS)] == FIXED_BIN_COUNTS
+            assert kind == "log" or n < 7 or s["lo"] < 0
+    assert {1, 20, 127, 128, 129, 136, 255, 256, 257, 1023, 4097, 8191, 8192, 8193, 9999, 10000} <= set(FIXED_BIN_COUNTS)
+    ranges = [s for s in sets if s["name"].startswith("range_")]
+    assert len(ranges) >= 40 and all(np.array_equal(s["values"], np.arange(s["lo"], s["hi"] + 1)) for s in ranges)
+    assert 20 in by_set["range_-5_-1"]
+    dups = [s for s in sets if s["name"].startswith("dup_")]
+    assert len(dups) >= 2 and all(len(np.unique(s["values"])) * 20 < len(s["values"]) for s in dups)
+    # many values exactly on inner edges
+    s = next(s for s in sets if s["name"] == "dup_quarters")
+    _, e = B.edges(s["lo"], s["hi"], 32)
+    assert np.isin(s["values"], e[1:-1]).sum() > 1000
+    (_, full, first, cost), (_, ld, ld_first, ld_cost) = searches()
+    assert len(full) == 3552 and first == 10 and len(cost) == 9991 and ld_first == 10 and len(ld_cost) == 991 and len(ld) > 100
+    assert 10 + int(np.flatnonzero(cost == cost.min())[0]) == int(chain_golden()["b_scalars"][5])
+    assert 10 + int(np.flatnonzero(ld_cost == ld_cost.min())[0]) == int(golden()["ld_n_bins"])
+
+
+def test_restatement_equals_golden():
+    sets = value_sets()
+    for c in cases():
+        s = sets[c["set"]]
+        hist = B.counts(s["sorted"], s["lo"], s["hi"], c["nb"])
+        assert np.array_equal(hist, c["hist"]) and hist.sum() == len(s["values"]), (s["name"], c["nb"])
+        assert _bits([B.cost_of(hist, len(s["values"]), s["lo"], s["hi"], c["nb"])])[0] == _bits([c["cost"]])[0], (s["name"], c["nb"])
+    for name, values, first, cost in searches():
+        a = np.sort(values)
+        got = [B.cost(a, a[0], a[-1], nb) for nb in range(first, first + len(cost))]
+        assert np.array_equal(_bits(got), _bits(cost)), name
+
+
+def test_slot_tree_of_the_kernel_equals_the_pairwise_sum():
+    """The kernel's layout of numpy's pairwise sum (one slot of a depth-7 tree per thread) against the recursion, at every
+    length at which the tree changes shape and at seeded ones.  A check of the design: both sides are Python
+    (_binsearch_reference.slot_tree_sum restates the kernel by hand), so this passes without the kernel and would not see the
+    kernel drift from the restatement.  What pins the kernel's own tree is tests/test_gpu_binsearch.py at more than 128 bins."""
+    rng = np.random.default_rng(3)
+    for n in list(range(1, 300)) + [511, 512, 513, 1023, 1024, 1025, 1031, 4095, 4096, 4103, 8183, 8184, 8185, 8191, 8192] + \
+            rng.integers(300, 8192, 60).tolist():
+        x = rng.normal(0.0, 50.0, n) ** 2
+        assert B.slot_tree_sum(x) == B.pairwise_sum(x) == float(np.add.reduce(x)), n
+
+
+def test_header_matches_binding_and_library():
+    from fluorosequencingimageanalysis_amd import _native, _native_binsearch as NB, lognormal as LN
+    hdr = open(os.path.join(ROOT, "include", "fsq_binsearch.h")).read()
+    declared = set(re.findall(r"\b(fsq_[a-z_0-9]+)\s*\(", hdr))
+    assert declared == set(NB.EXPORTED) == {"fsq_histogram_costs", "fsq_histogram_costs_sorted", "fsq_histogram_counts"}
+    if not os.path.exists(_native.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    for name in declared:
+        getattr(L, name)
+    assert int(re.search(r"#define FSQ_BINSEARCH_MAX_BINS (\d+)", hdr).group(1)) == NB.MAX_BINS == LN.MAX_BINS == B.MAX_BINS >= 10000
+    assert "fsq_binsearch.h" in open(os.path.join(ROOT, "fluorosequencingimageanalysis_amd", "csrc", "Makefile")).read()
+
+
+def test_c_abi_refuses_bad_arguments_before_a_launch():
+    """Every refusal returns FSQ_EINVAL on the host; the pointers are never touched (they point nowhere)."""
+    from fluorosequencingimageanalysis_amd import _native, _native_binsearch as NB
+    L = NB.lib()
+    p = ctypes.c_void_p(4096)
+    inf, nan, big = float("inf"), float("nan"), 1.7e308
+    bad_ranges = [(0, 0.0, 1.0), (-1, 0.0, 1.0), (1 << 31, 0.0, 1.0), (1 << 40, 0.0, 1.0), (5, 1.0, 1.0), (5, 2.0, 1.0), (5, -inf, 1.0),
+                  (5, 0.0, inf), (5, nan, 1.0), (5, 0.0, nan), (5, -big, big), (5, 0.0, 5e-324)]
+    for n, lo, hi in bad_ranges:
+        assert L.fsq_histogram_costs(p, n, lo, hi, p, 3, p, None) == _native.FSQ_EINVAL, (n, lo, hi)
+        assert L.fsq_histogram_counts(p, n, lo, hi, 10, p, None) == _native.FSQ_EINVAL, (n, lo, hi)
+    for nb in (0, -1, NB.MAX_BINS + 1, 1 << 30):
+        assert L.fsq_histogram_counts(p, 5, 0.0, 1.0, nb, p, None) == _native.FSQ_EINVAL, nb
+    assert L.fsq_histogram_costs(p, 5, 0.0, 1.0, p, -1, p, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_costs(p, 5, 0.0, 1.0, p, 0, p, None) == _native.FSQ_OK                 # nothing to do: no launch
+    assert L.fsq_histogram_costs(None, 5, 0.0, 1.0, p, 3, p, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_costs(p, 5, 0.0, 1.0, None, 3, p, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_costs(p, 5, 0.0, 1.0, p, 3, None, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_counts(None, 5, 0.0, 1.0, 10, p, None) == _native.FSQ_EINVAL
+    for n in (0, -1, 1 << 31, 1 << 40):                                                           # (its bounds are the kernel's to check)
+        assert L.fsq_histogram_costs_sorted(p, n, p, 3, p, None) == _native.FSQ_EINVAL, n
+    assert L.fsq_histogram_costs_sorted(p, 5, p, -1, p, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_costs_sorted(p, 5, p, 0, p, None) == _native.FSQ_OK
+    for args in ((None, 5, p, 3, p), (p, 5, None, 3, p), (p, 5, p, 3, None)):
+        assert L.fsq_histogram_costs_sorted(*args, None) == _native.FSQ_EINVAL
+    assert L.fsq_histogram_counts(p, 5, 0.0, 1.0, 10, None, None) == _native.FSQ_EINVAL
+
+
+@pytest.fixture
+def no_torch(monkeypatch):
+    """Any use of torch by the package fails: what passes with it ran on the host alone."""
+    from fluorosequencingimageanalysis_amd import engine
+
+    def boom():
+        raise AssertionError("the device route was taken")
+    monkeypatch.setattr(engine, "_torch", boom)
+
+
+def test_python_refuses_bad_arguments_before_a_launch(no_torch):
+    from fluorosequencingimageanalysis_amd import lognormal as LN
+    ok = [1, 5, 9, -3]
+    for values, match in (([], "at least one value"), ([1.0, float("nan")], "finite"), ([1.0, float("inf")], "finite"),
+                          ([0, (1 << 53) + 1], "2\\^53"), ([-(1 << 53) - 1, 0], "2\\^53"), ([0, 1 << 70], "2\\^53|real values"),
+                          (np.array([0, (1 << 63) + 5], np.uint64), "2\\^53"), (["a", "b"], "real values"),
+                          ([1 + 2j, 3], "real values")):
+        for call in (lambda v: LN.histogram_costs(v, [10, 20], "cuda"), lambda v: LN.bin_search_records(v, 10, 20, "cuda"),
+                     lambda v: LN.histogram_counts(v, 10, "cuda")):
+            with pytest.raises(ValueError, match=match):
+                call(values)
+    for values in ([1.0, float("nan")], [float("nan"), 1.0], [float("inf"), 1.0], [0, (1 << 53) + 1]):
+        for call in (lambda v: LN.optimal_bin_size(v, device="cuda"), lambda v: LN.optimal_bin_count(v, device="cuda"),
+                     lambda v: LN._get_m0Dm1(v, device="cuda")):
+            with pytest.raises(ValueError, match="finite|2\\^53"):
+                call(values)
+    for counts, match in (([0], "1 \\.\\. 10000"), ([10, 10001], "1 \\.\\. 10000"), ([-5], "1 \\.\\. 10000"), ([], "non-empty"),
+                          ([1.5, 2.5], "integers"), ([[1, 2]], "1-D")):
+        with pytest.raises(ValueError, match=match):
+            LN.histogram_costs(ok, counts, "cuda")
+        with pytest.raises(ValueError, match=match):
+            LN.optimal_bin_size(ok, np.array(counts), device="cuda")
+    for args in ((0, 20), (10, 10001), (20, 10)):
+        with pytest.raises(ValueError):
+            LN.bin_search_records(ok, *args, device="cuda")
+    with pytest.raises(ValueError, match="1 \\.\\. 10000"):
+        LN.optimal_bin_count(ok, 10, 10001, device="cuda")
+    for nb in (0, -1, 10001):
+        with pytest.raises(ValueError, match="1 \\.\\. 10000"):
+            LN.histogram_counts(ok, nb, "cuda")
+    # the limits themselves pass the checks
+    assert LN._checked_values([-(1 << 53), 1 << 53]).tolist() == [-2.0 ** 53, 2.0 ** 53]
+    assert LN._checked_values((1, 2.5)).dtype == np.float64 and LN._checked_values(np.array([1, 2], np.float32)).dtype == np.float64
+    assert LN._checked_bin_counts([1, 10000]).dtype == np.int32
+
+
+def _outcome(f):
+    try:
+        with np.errstate(all="ignore"):
+            return f()
+    except Exception as e:  # noqa: BLE001
+        return type(e).__name__ + ": " + str(e)
+
+
+def test_equal_values_take_the_host_route_whatever_the_device(no_torch):
+    """max == min: the device route ends as the host route ends today, by being the host route."""
+    from fluorosequencingimageanalysis_amd import lognormal as LN
+    for raw in ((5, 5, 5), (2.5,), ()):
+        for f in (lambda d: LN.optimal_bin_size(raw, device=d)[2].tolist(), lambda d: LN.optimal_bin_count(raw, 10, 30, device=d),
+                  lambda d: LN._get_m0Dm1(raw, 12, device=d)):
+            host, dev = _outcome(lambda: f(None)), _outcome(lambda: f("cuda"))
+            assert str(host) == str(dev) and "device route" not in str(dev), (raw, host, dev)
+    phot = {"ch1": {0: {(1, 2): ((True, False), (7, 1), 1), (3, 4): ((True, False), (7, 2), 2)}}}
+    host, dev = _outcome(lambda: LN.last_drop_method_v2(phot)), _outcome(lambda: LN.last_drop_method_v2(phot, device="cuda"))
+    assert str(host) == str(dev) and "device route" not in str(dev)
+
+
+def test_without_a_device_the_four_functions_are_the_host_route(no_torch):
+    from fluorosequencingimageanalysis_amd import lognormal as LN
+    for f in (LN.optimal_bin_size, LN.optimal_bin_count, LN._get_m0Dm1, LN.last_drop_method_v2):
+        assert inspect.signature(f).parameters["device"].default is None
+    sets = value_sets()
+    by_set = {}
+    for c in cases():
+        by_set.setdefault(c["set"], []).append(c)
+    for si, cs in by_set.items():
+        s = sets[si]
+        if len(s["values"]) > 300:
+            continue
+        nbs = np.array([c["nb"] for c in cs])
+        for kw in ({}, {"device": None}):
+            min_cost, where, cost = LN.optimal_bin_size(raw_of(s), nbs, **kw)
+            assert cost.shape == (len(nbs), 1) and np.array_equal(_bits(cost[:, 0]), _bits([c["cost"] for c in cs])), s["name"]
+            assert min_cost == cost.min() and np.array_equal(where[0], np.flatnonzero(cost[:, 0] == cost.min()))
+    g, cg = golden(), chain_golden()
+    ld = tuple(g["ld_values"].tolist())
+    assert LN.optimal_bin_count(ld) == LN.optimal_bin_count(ld, 10, 1000, None) == int(g["ld_n_bins"])
+    raw = tuple(int(x) for x in g["full_values"])
+    m0 = LN._get_m0Dm1(raw, int(cg["b_scalars"][5]), device=None)
+    assert m0 == LN._get_m0Dm1(raw, int(cg["b_scalars"][5])) and _bits([m0[7]])[0] == _bits(cg["b_scalars"][:1])[0]
+
+
+def _recorded_costs(values, bin_counts, device=None):
+    """lognormal.histogram_costs without a GPU: the recorded costs of the two recorded searches, the restatement for any other."""
+    a = np.sort(np.asarray(values, dtype=np.float64))
+    b = np.asarray(bin_counts)
+    for name, v, first, cost in searches():
+        if len(a) == len(v) and np.array_equal(a, np.sort(v)) and np.array_equal(b, np.arange(first, first + len(cost))):
+            return cost.copy()
+    return np.array([B.cost(a, a[0], a[-1], int(nb)) for nb in b])
+
+
+def test_command_line_on_both_routes(tmp_path, monkeypatch, capsys):
+    """--host_bin_search is parsed and keeps the searches on the host; with the device route (its costs stood in for) the
+    recorded chain comes out and every file is byte for byte the host route's."""
+    import torch
+    from fluorosequencingimageanalysis_amd import lognormal as LN, lognormal_fitter_v2 as CL
+    a = CL.make_parser().parse_args(["t.csv"])
+    assert a.host_bin_search is False and CL.make_parser().parse_args(["t.csv", "--host_bin_search"]).host_bin_search is True
+    b = CL.make_parser().parse_args(["t.csv", "--host_bin_search"])
+    assert CL._search_device(b, None) is None and CL._search_device(b, "cuda:1") is None and CL._search_device(a, "cuda:1") == "cuda:1"
+    for have in (True, False):
+        monkeypatch.setattr(torch.cuda, "is_available", lambda have=have: have)
+        assert CL._search_device(a, None) == ("cuda" if have else None)
+    monkeypatch.undo()
+
+    def records(intensities, categories, means, beta_sigma, max_possible=5, allow_multidrop=True, max_deviation=3, budget=1 << 22,
+                lengths=None, device=None):
+        return restated_records(R, intensities, categories, means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
+    monkeypatch.setattr(LN, "lognormal_records", records)
+    seen = []
+
+    def costs(values, bin_counts, device=None):
+        seen.append((len(values), len(bin_counts), device))
+        return _recorded_costs(values, bin_counts, device)
+    monkeypatch.setattr(LN, "histogram_costs", costs)
+    g = chain_golden()
+    out = {}
+    path = tmp_path / "track_photometries_abc123.csv"
+    path.write_text(chain_csv_text())
+    for route, extra in (("device", []), ("host", ["--host_bin_search"])):
+        res = CL.main(["lognormal_fitter_v2.py", str(path)] + extra, timestamp_epoch=1500000000, device="cuda")
+        text = capsys.readouterr().out
+        if route == "device":
+            assert [s[1:] for s in seen] == [(9991, "cuda"), (991, "cuda"), (991, "cuda")] and seen[0][0] == 3552
+        else:
+            assert len(seen) == 3                                   # nothing more went to the device
+        check_fit_against_record(res["original_plf_results"], "b_fit0_")
+        check_fit_against_record(res["plf_results"], "b_fit1_")
+        assert np.array_equal(_bits([res["alpha"], res["original_beta"], res["original_beta_sigma"], res["adj_beta"],
+                                     res["adj_beta_sigma"]]), _bits(g["b_scalars"][:5]))
+        base = res["output_filepath_base"]
+        names = sorted(f[len(os.path.basename(base)):] for f in os.listdir(tmp_path) if f.startswith(os.path.basename(base)))
+        assert names == ["CLUSTERED.csv", "COMMANDLINE.pkl", "INTERMEDIATES_v2.pkl", "RAW_PHOTOMETRIES.pkl", "SIGNALS.pkl"]
+        out[route] = ({n: open(base + n, "rb").read() for n in names}, text)
+        for n in names:
+            os.unlink(base + n)
+    same_files_but_for_the_flag(out["device"][0], out["host"][0])
+    assert out["device"][1] == out["host"][1]
