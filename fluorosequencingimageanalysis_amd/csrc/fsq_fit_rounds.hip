@@ -25,6 +25,7 @@
 
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "fsq_common.h"
@@ -683,7 +684,17 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
             WAVE_SYNC();
             unsigned pos = 0x76543210u;         // slot -> position
             bool broken = false;
-            for (int j = 0; j < n7; j++) {
+            // Four lanes: at step j only the 6 - j columns at positions > j and f still take the Householder pass, and an
+            // instruction is issued for the wave whatever the number of lanes that need it.  From step 3 on at most four
+            // slots are live per fit - positions 4, 5, 6 and f - so at step 3, once its pivot column is published, they are
+            // moved into register set 0, one per lane (positions 4, 5, 6 to lanes 0, 1, 2 of the quad, f to lane 3), and
+            // steps 3 .. 6 run the pass, the shift and the publication on that set alone (CMP below); set 1 is dead from
+            // there.  my_slot is the slot a lane's set 0 holds after the move, lane_of the lane that holds a slot.
+            constexpr bool COMPACT = (L == 4);
+            int my_slot = cl;
+            unsigned lane_of = 0x32103210u;
+            auto qr_step = [&](const int j, auto cmp_tag) __attribute__((always_inline)) {
+                constexpr bool CMP = COMPACT && decltype(cmp_tag)::value;
                 const int len = FSQ_NPIX - j;
                 if (REGPOS && !broken) {
                     // candidates: positions j .. 6 (norms are >= +0; a NaN among them sends the fit to the exact kernel, where
@@ -753,21 +764,21 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 }
                 RPH_MARK(7)
                 const int lj = nib_get(ipvt, j);
-                const int owner = gbase + (lj % L);
+                const int owner = gbase + (CMP ? nib_get(lane_of, lj) : lj % L);
                 // The lane that owns the pivot column publishes it in LDS (the Q_DATA slots: the pixels are not needed again
                 // in this pass) together with its norm; the group then turns it into the Householder vector row-parallel
                 // (lane cl scales rows cl, cl + L, ...) and every lane reads the vector from there, so no lane keeps a third
                 // 25-row column in registers and the scaling is not one lane's work.  (Letting every lane take the norm from
                 // the published column instead - no select between the owner's register sets - was measured 2 % slower.)
                 bool brk = false;
-                if (lane == owner) {
-                    double t[FSQ_NPIX];
-#pragma unroll
-                    for (int i = 0; i < FSQ_NPIX; i++) t[i] = (NC == 2 && (lj / L) != 0) ? col[NC - 1][i] : col[0][i];
+                auto publish = [&](const double* t) __attribute__((always_inline)) {
 #pragma unroll
                     for (int i = 0; i < FSQ_NPIX; i++) { QL(Q_DATA, i) = t[i]; KA_ROWS(i); }
                     if (!broken) {
-                        double ajnorm = fsq_sqrt(dot_regcol(t, len));
+                        // (step 0: the column is the one whose acnorm the same sum over the same 25 values gave just above)
+                        double ajnorm;
+                        if (!CMP && j == 0) ajnorm = QL(Q_ACN, lj);
+                        else ajnorm = fsq_sqrt(dot_regcol(t, len));
                         if (ajnorm == 0) brk = true;                // mpfit.py:1790 `break`
                         else {
                             if (t[0] < 0) ajnorm = -ajnorm;
@@ -775,9 +786,32 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                             QL(Q_TMP, 6) = ajnorm;
                         }
                     }
+                };
+                if (lane == owner) {
+                    if (CMP && j > 3) publish(col[0]);              // (after the move: no select between the register sets)
+                    else {
+                        double t[FSQ_NPIX];
+#pragma unroll
+                        for (int i = 0; i < FSQ_NPIX; i++) t[i] = (NC == 2 && (lj / L) != 0) ? col[NC - 1][i] : col[0][i];
+                        publish(t);
+                    }
                 }
                 WAVE_SYNC();
                 broken = broken || (__shfl((int)brk, owner) != 0);
+                if (CMP && j == 3) {
+                    // the move: lane cl takes the column of slot ns from the lane and the register set that hold it.  Rows 22 .. 24
+                    // are +0 in every column by now (three shifts), so they stay where they are.
+                    const int ns = (cl < 3) ? nib_get(ipvt, 4 + cl) : 7;
+                    const int src = gbase + (ns & 3);
+                    const bool hi = (ns >> 2) != 0;
+#pragma unroll
+                    for (int i = 0; i < FSQ_NPIX - 3; i++) {
+                        const double a = __shfl(col[0][i], src), b = __shfl(col[NC - 1][i], src);
+                        col[0][i] = hi ? b : a;
+                    }
+                    my_slot = ns;
+                    lane_of = nib_set(nib_set(nib_set(lane_of, nib_get(ipvt, 4), 0), nib_get(ipvt, 5), 1), nib_get(ipvt, 6), 2);
+                }
                 int emin_s = 0;                                     // FAST: lower bound of the scaled reflector's exponents
                 if (!broken) {
                     const double ajn = QL(Q_TMP, 6);
@@ -809,8 +843,8 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 const FsqDivisor kj = fsq_divisor(ajj0);
                 if (FAST) KA_HZ(8, !fsq_divisor_in_range(ajj0));
 #pragma unroll
-                for (int pass = 0; pass < NC; pass++) {
-                    const int slot = cl + L * pass;
+                for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
+                    const int slot = CMP ? my_slot : cl + L * pass;
                     const bool is_f = (slot == 7);
                     const int k = is_f ? 7 : nib_get(pos, slot);
                     const bool todo = is_f ? true : (!broken && k > j);
@@ -896,8 +930,8 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 for (int sub = 0; sub < NSUB; sub++) any_redo |= redo[sub];
                 if (any_redo) {
 #pragma unroll
-                    for (int pass = 0; pass < NC; pass++) {
-                        const int slot = cl + L * pass;
+                    for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
+                        const int slot = CMP ? my_slot : cl + L * pass;
                         const int k = (slot < 7) ? nib_get(pos, slot) : 0;
                         const int ix = REGPOS ? k : k - j - 1;      // (which lane looked at position k, and in which of its two turns)
                         if (slot < 7 && k > j && ((redo[(NSUB == 2) ? ix / L : 0] >> (gbase + ix % L)) & 1ull)) {
@@ -924,14 +958,17 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     QL(Q_R, j * 7 + lj) = QL(Q_RDIAG, j);           // fjac[j, lj] = rdiag[j] (mpfit.py:1123)
                 }
 #pragma unroll
-                for (int pass = 0; pass < NC; pass++) {
+                for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
 #pragma unroll
                     for (int i = 0; i + 1 < FSQ_NPIX; i++) col[pass][i] = col[pass][i + 1];
                     col[pass][FSQ_NPIX - 1] = 0.0;
                 }
                 WAVE_SYNC();
                 RPH_MARK(11)
-            }
+            };
+            for (int j = 0; j < (COMPACT ? 3 : n7); j++) qr_step(j, std::false_type{});
+            if (COMPACT)
+                for (int j = 3; j < n7; j++) qr_step(j, std::true_type{});
             RPH_MARK(4)
             // ---- first iteration scaling, gradient test (mpfit.py:1099-1160) -----------------------
 #define QRG(i, k) QL(Q_R, (i) * 7 + nib_get(ipvt, (k)))
