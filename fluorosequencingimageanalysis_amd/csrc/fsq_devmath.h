@@ -87,9 +87,10 @@ FSQ_DEV double fsq_exp(double x) { return fsq_exp_core<false>(x, 0.0); }
 // inf / nan returns.  The LM model never gets there (sigma >= 0.75 and centres in [2, 3] bound the exponent by 64), so
 // anything outside |x| < 512 (NaN included) only raises *bad and the caller redoes the fit with fsq_exp.
 // fsq_selftest_exp compares the two over the whole double range.
-FSQ_DEV double fsq_exp_bf(double x, bool* bad)
+// fsq_exp_bf_unchecked is that arithmetic alone, for callers that have PROVED |x| < 512 beforehand (fsq_evalguard.h does it
+// once per model evaluation); fsq_exp_bf checks the argument itself.
+FSQ_DEV double fsq_exp_bf_unchecked(double x)
 {
-    *bad = *bad || !(__builtin_fabs(x) < 512.0);
     double kd = fsq_fma(x, EXP_INVLN2N, EXP_SHIFT);
     unsigned long long ki = fsq_bits(kd);
     kd -= EXP_SHIFT;
@@ -107,6 +108,11 @@ FSQ_DEV double fsq_exp_bf(double x, bool* bad)
     tmp = fsq_fma(r2 * r2, p45, tmp);
     double scale = fsq_dbl(sbits);
     return fsq_fma(scale, tmp, scale);
+}
+FSQ_DEV double fsq_exp_bf(double x, bool* bad)
+{
+    *bad = *bad || !(__builtin_fabs(x) < 512.0);
+    return fsq_exp_bf_unchecked(x);
 }
 
 // ---- division by a shared divisor --------------------------------------------------------------------------
@@ -141,6 +147,17 @@ FSQ_DEV double fsq_div_by(double n, const FsqDivisor& k)
     double rem = fsq_fma(-k.d, q, n);
     q = fsq_fma(rem, k.r, q);
     return __builtin_amdgcn_div_fixup(q, k.d, n);
+}
+// The SQUARE of n / d without the v_div_fixup: for finite n and d inside the guarded ranges (fsq_evalguard.h proves them
+// for the model's numerators) the fix-up passes the quotient through unchanged, except that for n = 0 it sets the sign of
+// the zero - which squaring discards.  Only the square is returned so that the unfixed quotient cannot reach any other
+// use: do NOT build a general quotient out of this (the fdjac2 quotients keep fsq_div_by, their signed zeros reach R).
+FSQ_DEV double fsq_sq_of_quotient_ranges_proved(double n, const FsqDivisor& k)
+{
+    double q = n * k.r;
+    double rem = fsq_fma(-k.d, q, n);
+    q = fsq_fma(rem, k.r, q);
+    return q * q;
 }
 // FAST = false: the plain division (same call sites, used by the exact build of a kernel)
 template <bool FAST> FSQ_DEV double fsq_div_sel(double n, const FsqDivisor& k) { return FAST ? fsq_div_by(n, k) : n / k.d; }

@@ -30,6 +30,7 @@
 
 #include "fsq_common.h"
 #include "fsq_lm_quad.h"
+#include "fsq_evalguard.h"
 
 namespace {
 
@@ -319,13 +320,22 @@ FSQ_DEV bool fsq_square_is_pow2(double t, double sq, double lo)
 }
 
 // exp(-(u^2 + v^2) / 2) of one model pixel from the numerators of its two rotated offsets (gaussfitter.py:128-135)
+// FAST: no per-pixel range checks - the caller has put the evaluation's scalars (rotation, rotated centre, sigmas) through
+// fsq_evalguard_ok (fsq_evalguard.h), which proves the numerators' exponents, the quotients' ranges and |e| < 512 for all 25
+// pixels at once; where it fails the caller discards what is computed here and the fit takes the exact path.
 template <bool FAST>
-FSQ_DEV double ka_gauss(double nu, double nv, const FsqDivisor& k4, const FsqDivisor& k5, int* em, bool* bad)
+FSQ_DEV double gauss_usq(double n, const FsqDivisor& k)       // (n / d)^2
 {
-    if (FAST) { *em = min(*em, fsq_expo(nu)); *em = min(*em, fsq_expo(nv)); }
-    const double u = fsq_div_sel<FAST>(nu, k4), v = fsq_div_sel<FAST>(nv, k5);
-    const double e = -(u * u + v * v) / 2.;
-    return FAST ? fsq_exp_bf(e, bad) : fsq_exp(e);
+    if (FAST) return fsq_sq_of_quotient_ranges_proved(n, k);
+    const double q = n / k.d;
+    return q * q;
+}
+template <bool FAST>
+FSQ_DEV double gauss_exp(double e) { return FAST ? fsq_exp_bf_unchecked(e) : fsq_exp(e); }
+template <bool FAST>
+FSQ_DEV double ka_gauss(double nu, double nv, const FsqDivisor& k4, const FsqDivisor& k5)
+{
+    return gauss_exp<FAST>(-(gauss_usq<FAST>(nu, k4) + gauss_usq<FAST>(nv, k5)) / 2.);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -338,7 +348,8 @@ FSQ_DEV double ka_gauss(double nu, double nv, const FsqDivisor& k4, const FsqDiv
 // wave latency, not instruction count - hence the 8-lane form, which trades ~1.4x the instructions per fit for twice the
 // waves.
 // FAST = true: divisions by a shared divisor go through fsq_div_by (fsq_devmath.h) and every operand range that
-// makes it bit-identical to `/` is checked on the way; a group that leaves those ranges writes nothing and appends
+// makes it bit-identical to `/` is checked on the way (for the model evaluations: proved once per evaluation from its
+// scalars, fsq_evalguard.h - their pixels carry no checks); a group that leaves those ranges writes nothing and appends
 // a copy of its queue-A record to the slow queue SQ, which the FAST = false build (plain divisions, libm pow, same code)
 // works off when the host next looks (fits are independent, so a fit may fall a few rounds behind).
 // The FAST build also zeroes the queue counters of the next round (nobody reads or appends to them during kA).
@@ -377,6 +388,12 @@ FSQ_DEV double kag_dot25(const double* lds, int grp, int off)
 // pull all 25 LDS reads of a loop to its top); KA_PIN: keeps a running exponent minimum a chain (left to itself the
 // optimiser turns it into one tree at the end of the kernel and keeps every numerator alive for it)
 #define KA_ROWS(i) do { if (L == 8 && ((i) % 5) == 4) __builtin_amdgcn_sched_barrier(0); } while (0)
+// KA_EVAL_LOOP: the pixel loops of the model evaluations.  The fast four-lane kernel runs them fully unrolled and WITHOUT the
+// `pixel < 25` branch (EVAL_ALL: a lane whose last pixel would be 25 .. 27 evaluates pixel 24 again - same scalars, same
+// bits, stored to the same LDS word as its owner's), so that all 14 - 21 exp chains of a phase are one basic block the
+// scheduler can interleave; without per-pixel exponent tracking that fits the registers (218 VGPRs, no scratch - with the
+// tracking's min tree it spilled 160 bytes).  Every other instantiation keeps the rolled, guarded loops.
+#define KA_EVAL_LOOP _Pragma("unroll EVAL_UNROLL")
 #define KA_PIN(v) do { if (FAST) asm volatile("" : "+v"(v)); } while (0)
 // a guarded operand range was left / a decision could not be settled: the fit goes to the plain-division kernel.  -DFSQ_DEBUG_HZ
 // counts the reasons (fsq_debug_hz; tools/hz_reasons.py)
@@ -395,6 +412,9 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
     constexpr int NC = 8 / L;                   // columns per lane
     constexpr int MPX = (FSQ_NPIX + L - 1) / L; // pixels per lane when a 25-pixel job is split over the group
     constexpr int MREC = (A_HDR + L - 1) / L;   // record fields per lane (the header; E is fetched by pixel)
+    constexpr bool EVAL_ALL = FAST && L == 4;   // (see KA_EVAL_LOOP)
+    constexpr int EVAL_UNROLL = EVAL_ALL ? MPX : 1;
+    static_assert(fsq_llim(4, 0.) == FSQ_EG_MIN_SIGMA && fsq_llim(5, 0.) == FSQ_EG_MIN_SIGMA, "fsq_evalguard.h: sigma floor != the fit's lower limit");
     __shared__ double lds[Q_KA_END * G];
     const int lane = threadIdx.x, grp = lane / L, cl = lane % L, gbase = lane - cl;
     const int n7 = FSQ_NP;
@@ -491,7 +511,6 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 if (k >= 2 && (xx[k] > ul - h_)) h_ = -h_;                   // mpfit.py:1582-1587
                 hh[k] = h_;
             }
-            bool bad = false;
             double sn, cs;
             fsq_sincos(FSQ_PI_180 * xx[6], &sn, &cs);
             const double rcx = xx[3] * cs - xx[2] * sn, rcy = xx[3] * sn + xx[2] * cs;
@@ -499,6 +518,9 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
             if (FAST)       // |numerator| <= |p2| + |p3| + 8: bounded once the centre is
                 hz = hz || !fsq_divisor_in_range(xx[4]) || !fsq_divisor_in_range(xx[5]) || !(__builtin_fabs(xx[2]) <= 0x1p100) ||
                      !(__builtin_fabs(xx[3]) <= 0x1p100);
+            // the model evaluations below carry no per-pixel range checks: each one's scalars go through the predicate of
+            // fsq_evalguard.h instead (here the base point: fresh-fit evaluation and the sigma columns' shared numerators)
+            if (FAST) KA_HZ(15, !fsq_evalguard_ok(cs, sn, rcx, rcy, xx[4], xx[5]));
             {   // the pixels and E have arrived by now: lane cl converts its 32 / L pixels of the ROI copy
                 const unsigned w[4] = {roi.x, roi.y, roi.z, roi.w};
                 const unsigned w32[8] = {roi.x, roi.y, roi.z, roi.w, roi_hi.x, roi_hi.y, roi_hi.z, roi_hi.w};
@@ -515,14 +537,14 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
             WAVE_SYNC();
             if (__ballot(fresh)) {          // mpfit's first function call (mpfit.py:999): E at x0 (whole batches are fresh together)
                 if (fresh) {
-#pragma unroll 1
+                    KA_EVAL_LOOP
                     for (int m = 0; m < MPX; m++) {
-                        const int i = cl + L * m;
-                        if (i < FSQ_NPIX) {
+                        const int i = EVAL_ALL ? min(cl + L * m, FSQ_NPIX - 1) : cl + L * m;
+                        if (EVAL_ALL || i < FSQ_NPIX) {
                             const int xi = i / 5;
                             const double x = (double)xi, y = (double)(i - 5 * xi);
                             const double xp = x * cs - y * sn, yp = x * sn + y * cs;
-                            const double E = ka_gauss<FAST>(rcx - xp, rcy - yp, k4, k5, &emin, &bad);
+                            const double E = ka_gauss<FAST>(rcx - xp, rcy - yp, k4, k5);
                             QL(Q_FVEC, i) = E;
                         }
                     }
@@ -535,16 +557,17 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 const double rcx2 = xx[3] * cs - x2p * sn, rcy2 = xx[3] * sn + x2p * cs;
                 const double rcx3 = x3p * cs - xx[2] * sn, rcy3 = x3p * sn + xx[2] * cs;
                 if (FAST) KA_HZ(0, !(__builtin_fabs(x2p) <= 0x1p100) || !(__builtin_fabs(x3p) <= 0x1p100));
-#pragma unroll 1
+                if (FAST) KA_HZ(15, !fsq_eg_centre_ok(rcx2, rcy2) || !fsq_eg_centre_ok(rcx3, rcy3));       // (same rotation and sigmas as the base point)
+                KA_EVAL_LOOP
                 for (int m = 0; m < MPX; m++) {
-                    const int i = cl + L * m;
-                    if (i < FSQ_NPIX) {
+                    const int i = EVAL_ALL ? min(cl + L * m, FSQ_NPIX - 1) : cl + L * m;
+                    if (EVAL_ALL || i < FSQ_NPIX) {
                         const int xi = i / 5;
                         const double x = (double)xi, y = (double)(i - 5 * xi);
                         const double xp = x * cs - y * sn, yp = x * sn + y * cs;
                         const double d = QL(Q_DATA, i);
-                        const double E2 = ka_gauss<FAST>(rcx2 - xp, rcy2 - yp, k4, k5, &emin, &bad);
-                        const double E3 = ka_gauss<FAST>(rcx3 - xp, rcy3 - yp, k4, k5, &emin, &bad);
+                        const double E2 = ka_gauss<FAST>(rcx2 - xp, rcy2 - yp, k4, k5);
+                        const double E3 = ka_gauss<FAST>(rcx3 - xp, rcy3 - yp, k4, k5);
                         QL(Q_STAGE, i) = d - (xx[0] + xx[1] * E2);
                         QL(Q_STAGE + 25, i) = d - (xx[0] + xx[1] * E3);
                     }
@@ -578,22 +601,21 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 fsq_sincos(FSQ_PI_180 * (xx[6] + hh[6]), &snt, &cst);
                 const double rcxt = xx[3] * cst - xx[2] * snt, rcyt = xx[3] * snt + xx[2] * cst;
                 if (FAST) KA_HZ(1, !fsq_divisor_in_range(x4p) || !fsq_divisor_in_range(x5p));
-#pragma unroll 1
+                if (FAST) KA_HZ(15, !fsq_eg_sigma_ok(x4p) || !fsq_eg_sigma_ok(x5p) || !fsq_eg_rotation_ok(cst, snt) || !fsq_eg_centre_ok(rcxt, rcyt));
+                KA_EVAL_LOOP
                 for (int m = 0; m < MPX; m++) {
-                    const int i = cl + L * m;
-                    if (i < FSQ_NPIX) {
+                    const int i = EVAL_ALL ? min(cl + L * m, FSQ_NPIX - 1) : cl + L * m;
+                    if (EVAL_ALL || i < FSQ_NPIX) {
                         const int xi = i / 5;
                         const double x = (double)xi, y = (double)(i - 5 * xi);
                         const double xp = x * cs - y * sn, yp = x * sn + y * cs;
                         const double nu = rcx - xp, nv = rcy - yp;
-                        if (FAST) { emin = min(emin, fsq_expo(nu)); emin = min(emin, fsq_expo(nv)); }
-                        const double ub = fsq_div_sel<FAST>(nu, k4), vb = fsq_div_sel<FAST>(nv, k5);
-                        const double u4 = fsq_div_sel<FAST>(nu, k4p), v5 = fsq_div_sel<FAST>(nv, k5p);
-                        const double e4 = -(u4 * u4 + vb * vb) / 2., e5 = -(ub * ub + v5 * v5) / 2.;
-                        const double E4 = FAST ? fsq_exp_bf(e4, &bad) : fsq_exp(e4);
-                        const double E5 = FAST ? fsq_exp_bf(e5, &bad) : fsq_exp(e5);
+                        const double ub2 = gauss_usq<FAST>(nu, k4), vb2 = gauss_usq<FAST>(nv, k5);
+                        const double u42 = gauss_usq<FAST>(nu, k4p), v52 = gauss_usq<FAST>(nv, k5p);
+                        const double E4 = gauss_exp<FAST>(-(u42 + vb2) / 2.);
+                        const double E5 = gauss_exp<FAST>(-(ub2 + v52) / 2.);
                         const double xpt = x * cst - y * snt, ypt = x * snt + y * cst;
-                        const double Et = ka_gauss<FAST>(rcxt - xpt, rcyt - ypt, k4, k5, &emin, &bad);
+                        const double Et = ka_gauss<FAST>(rcxt - xpt, rcyt - ypt, k4, k5);
                         const double d = QL(Q_DATA, i);
                         QL(Q_STAGE, i) = d - (xx[0] + xx[1] * E4);
                         QL(Q_STAGE + 25, i) = d - (xx[0] + xx[1] * E5);
@@ -608,7 +630,6 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     for (int i = 0; i < FSQ_NPIX; i++) { col[NC - 1][i] = QL((s47 < 7) ? Q_STAGE + 25 * (s47 - 4) : Q_FVEC, i); KA_ROWS(i); }
                 }
             }
-            if (FAST) KA_HZ(2, bad);
             double hcol[NC];
 #pragma unroll
             for (int pass = 0; pass < NC; pass++) {
@@ -1059,6 +1080,7 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
 #undef REFL
 #undef KA_ROWS
 #undef KA_PIN
+#undef KA_EVAL_LOOP
 #undef KA_HZ
 #pragma pop_macro("QL")
 
@@ -1086,8 +1108,9 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
 // lane's LDS column (the residuals data - (p0 + p1 * E) are formed by the caller; E is also what an accepted step leaves
 // in the queue-A record for the next Jacobian round).
 // FAST: the model's two divisions per pixel share their divisors (sigma_h, sigma_w, inside [0.75, 2] by the bounds) ->
-// fsq_div_by, and exp is the branch-free fsq_exp_bf; the operand ranges in which those equal `/` and exp() bit for bit
-// are checked on the way and the return value is true when one was left - the caller then repeats the evaluation with
+// the hoisted-reciprocal quotient, and exp is the branch-free one; the operand ranges in which those equal `/` and exp() bit
+// for bit are proved up front from the trial point's scalars (fsq_evalguard.h: one predicate instead of three checks per
+// pixel) and the return value is true when the proof fails - the caller then repeats the evaluation with
 // FAST = false (plain divisions, full exp; same order of operations as fsq_model, gaussfitter.py:100-136).
 // Rows are a rolled loop (a fifth of the code) writing to LDS slots - no dynamically indexed register array, no scratch.
 FSQ_DEV int kb_res_slot(int i) { return i < 14 ? i : i + 7; }         // slots 14..20 hold the step vector wa1
@@ -1096,7 +1119,6 @@ template <bool FAST>
 FSQ_DEV bool kb_trial_gauss(const double* p, double* myscr)
 {
     bool bad = false;
-    int em = 0;
     double s, c;
     fsq_sincos(FSQ_PI_180 * p[6], &s, &c);
     const double rcen_x = p[3] * c - p[2] * s;
@@ -1104,7 +1126,7 @@ FSQ_DEV bool kb_trial_gauss(const double* p, double* myscr)
     const FsqDivisor k4 = fsq_divisor(p[4]), k5 = fsq_divisor(p[5]);
     if (FAST)       // |numerator| <= |p2| + |p3| + 8: bounded once the centre is
         bad = !fsq_divisor_in_range(p[4]) || !fsq_divisor_in_range(p[5]) || !(__builtin_fabs(p[2]) <= 0x1p100) ||
-              !(__builtin_fabs(p[3]) <= 0x1p100);
+              !(__builtin_fabs(p[3]) <= 0x1p100) || !fsq_evalguard_ok(c, s, rcen_x, rcen_y, p[4], p[5]);
 #pragma unroll 1
     for (int xi = 0; xi < 5; xi++) {
         const double x = (double)xi;
@@ -1114,14 +1136,9 @@ FSQ_DEV bool kb_trial_gauss(const double* p, double* myscr)
             const double xp = x * c - y * s;
             const double yp = x * s + y * c;
             const double nu = rcen_x - xp, nv = rcen_y - yp;
-            if (FAST) { em = min(em, fsq_expo(nu)); em = min(em, fsq_expo(nv)); }
-            const double u = fsq_div_sel<FAST>(nu, k4);
-            const double v = fsq_div_sel<FAST>(nv, k5);
-            const double e = -(u * u + v * v) / 2.;
-            myscr[kb_res_slot(xi * 5 + yi) * 64] = FAST ? fsq_exp_bf(e, &bad) : fsq_exp(e);
+            myscr[kb_res_slot(xi * 5 + yi) * 64] = ka_gauss<FAST>(nu, nv, k4, k5);
         }
     }
-    if (FAST) bad = bad || (em < -FSQ_DIV_EN);
     return bad;
 }
 
@@ -1561,6 +1578,38 @@ __global__ void kexpcheck(const double* __restrict__ x, long long n, unsigned lo
     if (wrong) atomicAdd(bad, 1ull);
 }
 }  // namespace
+
+// ---- self-test hook: the unchecked forms of the model evaluation against `/` and fsq_exp on operands inside the ranges
+// that fsq_evalguard.h proves (the caller supplies them): square of the quotient, exp ----------------------------------
+namespace {
+__global__ void kevalguardcheck(const double* __restrict__ num, const double* __restrict__ den, const double* __restrict__ x, long long n,
+                                unsigned long long* bad)
+{
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double q = num[i] / den[i];
+    if (fsq_bits(q * q) != fsq_bits(fsq_sq_of_quotient_ranges_proved(num[i], fsq_divisor(den[i])))) atomicAdd(bad, 1ull);
+    if (fsq_bits(fsq_exp(x[i])) != fsq_bits(fsq_exp_bf_unchecked(x[i]))) atomicAdd(bad + 1, 1ull);
+}
+}  // namespace
+
+extern "C" int fsq_selftest_evalguard(const double* d_num, const double* d_den, const double* d_x, int64_t n, int64_t* sq_mismatches,
+                                      int64_t* exp_mismatches, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (!d_num || !d_den || !d_x || !sq_mismatches || !exp_mismatches || n < 0) return FSQ_EINVAL;
+    unsigned long long* d_bad = nullptr;
+    FSQ_HIP_CHECK(hipMalloc((void**)&d_bad, 16));
+    FSQ_HIP_CHECK(hipMemsetAsync(d_bad, 0, 16, s));
+    if (n > 0) hipLaunchKernelGGL(kevalguardcheck, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_num, d_den, d_x, (long long)n, d_bad);
+    unsigned long long h[2] = {0, 0};
+    FSQ_HIP_CHECK(hipMemcpyAsync(h, d_bad, 16, hipMemcpyDeviceToHost, s));
+    FSQ_HIP_CHECK(hipStreamSynchronize(s));
+    (void)hipFree(d_bad);
+    *sq_mismatches = (int64_t)h[0];
+    *exp_mismatches = (int64_t)h[1];
+    return FSQ_OK;
+}
 
 extern "C" int fsq_selftest_exp(const double* d_x, int64_t n, int64_t* mismatches, void* stream)
 {

@@ -284,7 +284,7 @@ struct FsqLmState {
     int niter, nfev;
 };
 
-FSQ_DEV double fsq_llim(int j, double llim1) { return j == 0 ? 0.00 : j == 1 ? llim1 : j < 4 ? 2.00 : j < 6 ? 0.75 : 0.00; }
+constexpr FSQ_DEV double fsq_llim(int j, double llim1) { return j == 0 ? 0.00 : j == 1 ? llim1 : j < 4 ? 2.00 : j < 6 ? 0.75 : 0.00; }
 FSQ_DEV double fsq_ulim(int j) { return j < 2 ? 0.00 : j < 4 ? 3.00 : j < 6 ? 2.00 : 360.00; }
 FSQ_DEV bool fsq_qulim(int j) { return j >= 2; }
 

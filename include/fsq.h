@@ -332,6 +332,12 @@ int fsq_selftest_exp(const double* d_x, int64_t n, int64_t* mismatches, void* st
  * own error bound from a rounding boundary).  Counts the d_t[i] for which the predicate holds and pow(t, 2.0) != t * t
  * (must be 0), and those for which it does not hold (*undecided; about 3 % of random arguments). */
 int fsq_selftest_square(const double* d_t, int64_t n, int64_t* mismatches, int64_t* undecided, void* stream);
+/* fsq_selftest_evalguard: the model evaluation's forms without per-pixel checks (csrc/fsq_evalguard.h proves their
+ * operand ranges once per evaluation): counts the i for which the square of the unfixed hoisted-reciprocal quotient
+ * differs from (d_num[i] / d_den[i])^2, and those for which the unchecked branch-free exp differs from exp(d_x[i]).
+ * The caller supplies operands inside the proved ranges; both counts must be 0 there. */
+int fsq_selftest_evalguard(const double* d_num, const double* d_den, const double* d_x, int64_t n, int64_t* sq_mismatches,
+                           int64_t* exp_mismatches, void* stream);
 int64_t fsq_fit_last_slow_count(void);
 /* 1 when the library was built with the two single-launch A/B engines (make AB target, -DFSQ_BUILD_AB): only then do
  * FSQ_ENGINE_LANE / FSQ_ENGINE_QUAD select them; the shipped library returns FSQ_ENOTIMPL for those flags. */

@@ -14,7 +14,8 @@ from fluorosequencingimageanalysis_amd import _native as N, engine as E, pflib  
 
 NAMES = ["perturbed centre range", "perturbed sigma range", "exp argument range", "step h range", "height / amplitude range", "no pivot (NaN norms)",
          "pivot choice not settled by the tracked norms", "Householder norm range", "reflector head range", "update numerator exponents", "1 - t^2 is NaN",
-         "sign of 1 - t^2 not settled", "tracked error bound too large", "tiny numerators (exponent floor)", "re-computation test not settled"]
+         "sign of 1 - t^2 not settled", "tracked error bound too large", "tiny numerators (exponent floor)", "re-computation test not settled",
+         "model evaluation range predicate (fsq_evalguard.h; took over site 2)"]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 imgs = bench.make_fields(range(n), (512, 512), 500)
 eng = E.Engine(n, 512, 512)
