@@ -378,6 +378,24 @@ def unwind_photometries(photometries):
                 yield (channel, field, h, w, category, intensities, row)
 
 
+def write_photometries_dict_to_csv(photometries, filepath, dialect='excel'):
+    """MCsimlib.write_photometries_dict_to_csv (:5566-5586): one row per track in the dicts' order, the header's frame count
+    taken from the first track; returns the number of rows.  Floats are written as Python 2's str() wrote them."""
+    import csv
+    from .pflib import _py2_str
+    with open(filepath, 'w', newline='') as f:
+        output_writer = csv.writer(f, dialect=dialect)
+        cdict = next(iter(photometries.values()))
+        fdict = next(iter(cdict.values()))
+        category, intensities, row = next(iter(fdict.values()))
+        output_writer.writerow(['CHANNEL', 'FIELD', 'H', 'W', 'CATEGORY'] + ['FRAME ' + str(i) for i in range(len(category))])
+        row_counter = 0
+        for channel, field, h, w, category, intensities, row in unwind_photometries(photometries):
+            output_writer.writerow([str(channel), str(field), str(h), str(w), str(category)] + [_py2_str(i) for i in intensities])
+            row_counter += 1
+    return row_counter
+
+
 def photometries_lognormal_fit(photometries, beta, beta_sigma, max_possible=5, num_processes=None, allow_upsteps=False,
                                allow_multidrop=True, max_deviation=3, quench_factor=0, quench_factors=None,
                                budget=DEFAULT_BUDGET, device=None):

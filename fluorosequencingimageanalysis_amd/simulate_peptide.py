@@ -1,0 +1,159 @@
+"""Simulate fluorosequencing of one labelled peptide on the GPU and fit the simulated tracks: the reference's
+simulate_peptide.py.
+
+  python -m fluorosequencingimageanalysis_amd.simulate_peptide SEQUENCE LABELS [options]
+
+Writes Simulated_<hash>.pkl, a pickle (protocol 0) of (args, signals, molecular_error_signals): the parameters, what the
+lognormal fitter recovered and the molecular ground truth, and Simulated_<hash>.csv with the simulated photometries unless
+--no_csv.  Every option of the reference's parser is taken with its default; --distance_ddifs is accepted and has no effect
+(the reference passes it on under a name nothing reads) and -n is accepted and unused.  New: --seed (default: a fresh one;
+printed, and stored in the pickled args) makes a run repeatable, --host runs the NumPy twin of the kernels instead of the GPU."""
+import argparse
+import os
+import pickle
+import sys
+from datetime import datetime
+from math import log
+from time import time
+
+from . import peptide_simulator
+from .pflib import _epoch_to_hash
+
+MAX_POSSIBLE = 5                    # (simulate_peptide.py:197)
+MAX_DEVIATION = 3                   # (:283)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument('sequence', nargs=1, type=str, help="The peptide as a string of amino acids.")
+    p.add_argument('labels', nargs=1, type=str, help="The labelled amino acid (one letter).")
+    p.add_argument('-N', '--num_sims', type=int, default=100000, help="Number of molecules to simulate.")
+    p.add_argument('-m', '--num_mocks', type=int, default=4, help="Number of mocks performed.")
+    p.add_argument('-o', '--num_mocks_omitted', type=int, default=1, help="Number of mocks not imaged.")
+    p.add_argument('-e', '--num_edmans', type=int, default=8, help="Number of Edmans performed.")
+    p.add_argument('--edman_efficiency', type=float, default=0.90)
+    p.add_argument('--dye_destruction', type=float, default=0.1, help="Rate of dye destruction per cycle (not the exponent b).")
+    p.add_argument('--dud_dyes', type=float, default=0.50)
+    p.add_argument('--surface_degradation_1', type=float, default=0.30)
+    p.add_argument('--surface_degradation_1_num_cycles', type=int, default=3,
+                   help="Cycles (mock or Edman) under surface_degradation_1; surface_degradation_2 after them.")
+    p.add_argument('--surface_degradation_2', type=float, default=0.10)
+    p.add_argument('--fluor_intensity', type=float, default=70000, help="Intensity of one fluor.")
+    p.add_argument('--ddif_2', type=float, default=0.30, help="Dye-dye interaction factor of the second fluor.")
+    p.add_argument('--ddif_3', type=float, default=0.30, help="Dye-dye interaction factor of the third and further fluors.")
+    p.add_argument('--beta_sigma', type=float, default=0.20, help="Lognormal shape parameter.")
+    p.add_argument('--distance_ddifs', nargs='+', type=float, help="Accepted; without effect, as in the reference.")
+    p.add_argument('-n', '--num_processors', type=int, default=None, help="Accepted and unused.")
+    p.add_argument('--no_csv', action='store_true', default=False, help="Do not write the CSV of simulated photometries.")
+    p.add_argument('--output_directory', nargs=1, default=[os.getcwd()], help="Created if it does not exist.")
+    p.add_argument('--no_multidrop', action='store_true', default=False, help="No drops of more than one dye in the fit.")
+    p.add_argument('--superdye_rate', type=float, default=0.0, help="Chance of a dye being a superdye, 0 .. 1.")
+    p.add_argument('--superdye_factor', type=float, default=1.0, help="Superdyes are brighter by this factor.")
+    p.add_argument('--seed', type=int, default=None, help="Seed of the draws, 0 .. 2^64 - 1 (default: a fresh one).")
+    p.add_argument('--host', action='store_true', default=False, help="Run the NumPy twin of the kernels; no GPU needed.")
+    p.add_argument('--device', default=None, help="The torch device (default: cuda).")
+    return p
+
+
+def photometries_of_records(records):
+    """The dict simulate_peptide.py builds (:241-246) and the kept molecules' indices: track t is the t-th kept molecule,
+    channel 'ch1', field 0, H = W = t."""
+    fdict, kept = {}, []
+    cats, counts, inten = records["category"].tolist(), records["counts"].tolist(), records["intensity"].tolist()
+    for i, word in enumerate(cats):
+        if word == 0:
+            continue
+        t = len(kept)
+        fdict[(t, t)] = (tuple(c != 0 for c in counts[i]), tuple(inten[i]), t)
+        kept.append(i)
+    return {'ch1': {0: fdict}}, kept
+
+
+def molecular_error_signals_of_records(records, kept):
+    out = {}
+    counts = records["counts"].tolist()
+    for i in kept:
+        key = (peptide_simulator._decrements_of_row(counts[i]), counts[i][-1] == 0, counts[i][0])
+        out[key] = out.get(key, 0) + 1
+    return out
+
+
+def host_fit(photometries, beta, beta_sigma, max_possible, allow_multidrop, max_deviation, quench_factors):
+    """(signals, total_count, none_count) of lognormal.photometries_lognormal_fit with the Python restatement of the fit
+    (tests/_lognormal_reference.py of the source tree)."""
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "_lognormal_reference.py")
+    spec = importlib.util.spec_from_file_location("_lognormal_reference", path)
+    R = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(R)
+    means = [log(beta) + log(i + 1.0) - quench_factors[i] for i in range(max_possible + 2)]
+    signals, none_count, total = {}, 0, 0
+    for category, intensities, _ in photometries['ch1'][0].values():
+        signal, is_zero, _, _, _, _, start = R.intensities_to_signal(list(intensities), beta_sigma, max_possible, allow_multidrop,
+                                                                      max_deviation, category, means)
+        total += 1
+        if signal is None:
+            none_count += 1
+        else:
+            signals[(signal, is_zero, start)] = signals.get((signal, is_zero, start), 0) + 1
+    return signals, total, none_count
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.seed is None:
+        args.seed = peptide_simulator.fresh_seed()
+    sequence, labels = args.sequence[0], args.labels[0]
+    output_directory = os.path.abspath(args.output_directory[0])
+    if not os.path.exists(output_directory):
+        os.makedirs(output_directory)
+    allow_multidrop = not args.no_multidrop
+    output_filename = "Simulated_" + str(_epoch_to_hash(round(time()))) + ".pkl"
+    output_filepath = os.path.join(output_directory, output_filename)
+    ddif = [0, args.ddif_2] + [args.ddif_3] * 5
+    ep = dict(p=args.edman_efficiency, b=-log(1.0 - args.dye_destruction), u=args.dud_dyes, s=args.surface_degradation_1,
+              sc=args.surface_degradation_1_num_cycles, s2=args.surface_degradation_2, beta=args.fluor_intensity,
+              beta_sigma=args.beta_sigma, ddif=ddif, superdye_rate=args.superdye_rate, superdye_factor=args.superdye_factor)
+    shape = (sequence, labels, args.num_mocks - args.num_mocks_omitted, args.num_edmans, args.num_sims)
+    print("Seed: " + str(args.seed))
+    print("Parameters loaded. Starting simulation at " + str(datetime.now()))
+    csv_filepath = output_filepath[:-4] + ".csv"
+
+    def write_csv(photometries):
+        from . import lognormal
+        try:
+            rows = lognormal.write_photometries_dict_to_csv(photometries=photometries, filepath=csv_filepath)
+            print("Wrote " + str(rows) + " rows to " + str(csv_filepath))
+        except Exception as e:
+            import traceback
+            print("Failed to write simulated photometries to " + str(csv_filepath) + " due to exception " + str(e))
+            traceback.print_exc()
+
+    if args.host:
+        records = peptide_simulator.simulation_records(*shape, seed=args.seed, host=True, **ep)
+        photometries, kept = photometries_of_records(records)
+        molecular_error_signals = molecular_error_signals_of_records(records, kept)
+        if not args.no_csv:
+            write_csv(photometries)
+        print("Simulation complete. Fitting simulated tracks at " + str(datetime.now()))
+        signals, total_count, none_count = host_fit(photometries, args.fluor_intensity, args.beta_sigma, MAX_POSSIBLE, allow_multidrop,
+                                                    MAX_DEVIATION, ddif)
+    else:
+        out = peptide_simulator.simulate_and_fit_records(*shape, seed=args.seed, device=args.device, max_possible=MAX_POSSIBLE,
+                                                         allow_multidrop=allow_multidrop, max_deviation=MAX_DEVIATION,
+                                                         quench_factors=ddif, **ep)
+        if not args.no_csv:
+            sim = out["simulation"]
+            records = {k: sim[k].cpu().numpy() for k in ("category", "counts", "intensity")}
+            write_csv(photometries_of_records(records)[0])
+        print("Simulation complete. Fitting simulated tracks at " + str(datetime.now()))
+        signals, molecular_error_signals = out["signals"], out["molecular_error_signals"]
+    print("Fitting completed at " + str(datetime.now()) + ". Saving results to " + str(output_filename))
+    with open(output_filepath, 'wb') as f:
+        pickle.dump((args, signals, molecular_error_signals), f, protocol=0)
+    return output_filepath
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

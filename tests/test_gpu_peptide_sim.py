@@ -1,0 +1,244 @@
+"""Peptide Monte-Carlo simulation on the GPU (include/fsq_peptide_sim.h): bit for bit against the reference's recorded runs
+under the same draws (tests/golden/peptide_sim.npz) and against the NumPy twin (tests/_peptide_sim_reference.py); the chain
+into the lognormal fit and the command line.  Nothing is compared with a tolerance."""
+import contextlib
+import ctypes
+import math
+import os
+import pickle
+
+import numpy as np
+import pytest
+
+import _peptide_sim_reference as T
+from _peptide_sim_cases import golden_cases, random_twin_params, same_records
+from _util import _bits
+
+pytestmark = pytest.mark.gpu
+
+BASE = dict(length=8, label_mask=0b00100100, num_mocks=2, num_edmans=4, p=0.9, per_cycle_b=0.9, u=0.5, s=0.3, sc=3, s2=0.1,
+            log_beta=math.log(70000.0), beta_sigma=0.2, ddif=[0.0] + [0.3] * 14, superdye_rate=0.0, superdye_factor=1.0)
+
+
+@contextlib.contextmanager
+def _prefilled():
+    """Every output tensor the binding allocates starts as a byte pattern, not as zeros: what the kernel leaves unwritten shows."""
+    import torch
+    real = torch.empty
+
+    def filled(*a, **k):
+        t = real(*a, **k)
+        if t.is_cuda:
+            t.view(torch.uint8).fill_(0xA5)
+        return t
+    torch.empty = filled
+    try:
+        yield
+    finally:
+        torch.empty = real
+
+
+def _prm(kw, seed, first):
+    from fluorosequencingimageanalysis_amd import _native_peptide_sim as NP
+    prm = NP.FsqPeptideSimParams()
+    for k in ("label_mask", "p", "per_cycle_b", "u", "s", "s2", "log_beta", "beta_sigma", "superdye_rate", "superdye_factor", "length",
+              "num_mocks", "num_edmans", "sc"):
+        setattr(prm, k, kw[k])
+    prm.seed, prm.first_molecule, prm.n_ddif = seed, first, min(len(kw["ddif"]), 15)
+    for i, x in enumerate(kw["ddif"][:15]):
+        prm.ddif[i] = x
+    return prm
+
+
+def _device(kw, seed, first, n):
+    """fsq_peptide_simulate on pre-filled outputs, as host arrays."""
+    from fluorosequencingimageanalysis_amd import peptide_simulator as PS
+    with _prefilled():
+        out = PS.simulate_device_prm(_prm(kw, seed, first), n)
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+    host["edman_fail"], host["category"] = host["edman_fail"].view(np.uint64), host["category"].view(np.uint64)
+    return host
+
+
+def _against_twin(kw, seed, first, n, what=None):
+    got = _device(kw, seed, first, n)
+    exp = T.simulate(seed=seed, first_molecule=first, n_molecules=n, **kw)
+    same_records(got, exp, what)
+    return got
+
+
+def test_philox_known_answers_on_the_device():
+    import torch
+    from fluorosequencingimageanalysis_amd import peptide_simulator as PS
+    c = np.array([x[0] for x in T.KNOWN_ANSWERS], np.uint32)
+    k = np.array([x[1] for x in T.KNOWN_ANSWERS], np.uint32)
+    rng = np.random.default_rng(5)
+    c = np.concatenate([c, rng.integers(0, 2 ** 32, (500, 4), dtype=np.uint64).astype(np.uint32)])
+    k = np.concatenate([k, rng.integers(0, 2 ** 32, (500, 2), dtype=np.uint64).astype(np.uint32)])
+    with _prefilled():
+        got = PS.philox_words_device(torch.from_numpy(c.view(np.int32)).cuda(), torch.from_numpy(k.view(np.int32)).cuda())
+    got = got.cpu().numpy().view(np.uint32)
+    assert got[:3].tolist() == [list(x[2]) for x in T.KNOWN_ANSWERS]
+    assert np.array_equal(got, T.philox_np(c, k))
+
+
+@pytest.mark.parametrize("ci", range(6))
+def test_golden_through_c_abi(ci):
+    c = golden_cases()[ci]
+    got = _device(c["twin"], c["seed"], c["first"], c["n"])
+    same_records(got, dict(c["tables"], intensity=c["intensity"]), c["name"])
+    exp_log = np.array([[math.log(x) if x > 0 else -10000.0 for x in row] for row in c["intensity"].tolist()])
+    assert np.array_equal(_bits(got["log_intensity"]), _bits(exp_log))
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 1000])
+def test_random_parameter_sets_equal_the_twin(n):
+    rng = np.random.default_rng(1000 + n)
+    for rep in range(2):
+        kw = random_twin_params(rng)
+        _against_twin(kw, int(rng.integers(0, 2 ** 63)), int(rng.integers(0, 2 ** 40)), n, (n, rep))
+
+
+EDGES = {
+    "length_1": dict(length=1, label_mask=1),
+    "length_64_first_and_last": dict(length=64, label_mask=(1 << 63) | 1, num_edmans=20),
+    "no_labels": dict(label_mask=0),
+    "one_label_first": dict(label_mask=1),
+    "one_label_last": dict(label_mask=0b10000000),
+    "fifteen_labels": dict(length=40, label_mask=sum(1 << (2 * i) for i in range(15)), u=0.1, s=0.02, s2=0.01, per_cycle_b=0.97,
+                           num_edmans=12),
+    "no_mocks": dict(num_mocks=0),
+    "no_edmans": dict(num_edmans=0),
+    "one_frame": dict(num_mocks=0, num_edmans=0),
+    "64_frames": dict(num_mocks=13, num_edmans=50, length=64, label_mask=sum(1 << (4 * i + 1) for i in range(15)), u=0.05, s=0.01,
+                      s2=0.005, per_cycle_b=0.99),
+    "p_0": dict(p=0.0),
+    "p_1": dict(p=1.0),
+    "u_0": dict(u=0.0),
+    "u_1": dict(u=1.0),
+    "s_1": dict(s=1.0, u=0.0),
+    "sc_0": dict(sc=0),
+    "sc_beyond": dict(sc=64, s=0.05, s2=1.0),
+    "no_bleaching": dict(per_cycle_b=1.0),
+    "superdye_0": dict(superdye_rate=0.0, superdye_factor=2.5),
+    "superdye_half": dict(superdye_rate=0.5, superdye_factor=2.5, u=0.1),
+    "superdye_1": dict(superdye_rate=1.0, superdye_factor=2.5, u=0.1),
+    "shorter_than_edmans": dict(length=2, label_mask=0b11, num_edmans=9, p=0.95, u=0.1),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EDGES))
+def test_shape_and_parameter_edges(name):
+    kw = dict(BASE)
+    kw.update(EDGES[name])
+    got = _against_twin(kw, 4242, 7, 130, name)
+    F, L = kw["num_mocks"] + kw["num_edmans"] + 1, bin(kw["label_mask"]).count("1")
+    assert got["counts"].shape == (130, F) and got["loss_cycle"].shape == (130, L)
+    counts = got["counts"].astype(int)
+    # the edge does what its name says
+    if name == "s_1":
+        assert (counts[:, 1:] == 0).all() and (counts[:, 0] > 0).any()
+        assert set(got["loss_cause"].reshape(-1).tolist()) <= {T.CAUSE_DESTRUCTION, T.CAUSE_STRIP}
+    if name == "u_1" or name == "no_labels":
+        assert not counts.any() and not got["intensity"].any() and (got["log_intensity"] == -10000.0).all() and not got["category"].any()
+    if name == "u_0":
+        assert T.CAUSE_DUD not in got["loss_cause"].reshape(-1).tolist()
+    if name == "p_0":
+        assert T.CAUSE_EDMAN not in got["loss_cause"].reshape(-1).tolist() and (got["edman_fail"] == np.uint64(0b1111000)).all()
+    if name == "p_1":
+        assert not got["edman_fail"].any()
+    if name == "no_bleaching":
+        assert T.CAUSE_DESTRUCTION not in got["loss_cause"].reshape(-1).tolist()
+    if name == "shorter_than_edmans":
+        assert len(set(got["n_draws"][:, 0].tolist())) > 1          # Edman stops drawing once the molecule is empty
+    if name == "64_frames":
+        assert (counts[:, -1] > 0).any() and (got["category"] >> np.uint64(63)).any()
+    if name.startswith("superdye") and name != "superdye_0":
+        assert (got["n_draws"][:, 1] == counts[:, 0]).all() and counts[:, 0].max() == 2
+
+
+def test_first_molecule_chunks_and_carry():
+    whole = _device(BASE, 99, 1000, 300)
+    for part in range(3):
+        got = _device(BASE, 99, 1000 + 100 * part, 100)
+        same_records(got, {k: v[100 * part:100 * part + 100] for k, v in whole.items()}, part)
+    _against_twin(BASE, 31337, 2 ** 32 - 50, 100, "carry into counter word 2")
+
+
+def test_more_molecules_than_one_pass_of_the_grid():
+    """16 384 blocks of 64 molecules are launched at most: beyond that a block takes further chunks."""
+    kw = dict(BASE, num_mocks=1, num_edmans=1, length=3, label_mask=0b010)
+    n = 16384 * 64 + 70
+    got = _device(kw, 5, 0, n)
+    head = T.simulate(seed=5, first_molecule=0, n_molecules=130, **kw)
+    tail = T.simulate(seed=5, first_molecule=n - 200, n_molecules=200, **kw)
+    same_records({k: v[:130] for k, v in got.items()}, head, "head")
+    same_records({k: v[n - 200:] for k, v in got.items()}, tail, "tail")
+    assert abs(float((got["counts"][:, 0] > 0).mean()) - 0.45) < 0.01
+
+
+def test_invalid_shapes_return_einval_and_write_nothing():
+    import torch
+    from fluorosequencingimageanalysis_amd import _native as N
+    from fluorosequencingimageanalysis_amd import _native_peptide_sim as NP
+    bad = {"length_0": dict(length=0, label_mask=0), "length_65": dict(length=65), "sixteen_labelled": dict(length=20, label_mask=0xffff),
+           "65_frames": dict(num_mocks=30, num_edmans=34), "short_ddif": dict(ddif=[0.0]), "label_beyond_length": dict(label_mask=1 << 8),
+           "negative_mocks": dict(num_mocks=-1), "superdye_rate_2": dict(superdye_rate=2.0), "nan_p": dict(p=float("nan"))}
+    n = 10
+    bufs = [torch.empty(n * 64 * 8, dtype=torch.uint8, device="cuda") for _ in range(8)]
+    for name, change in bad.items():
+        kw = dict(BASE)
+        kw.update(change)
+        for b in bufs:
+            b.fill_(0xA5)
+        rc = NP.lib().fsq_peptide_simulate(ctypes.byref(_prm(kw, 1, 0)), n, *([b.data_ptr() for b in bufs] +
+                                                                              [torch.cuda.current_stream().cuda_stream]))
+        torch.cuda.synchronize()
+        assert rc == N.FSQ_EINVAL, name
+        assert all(bool((b == 0xA5).all()) for b in bufs), name
+    assert NP.lib().fsq_peptide_simulate(ctypes.byref(_prm(BASE, 1, 0)), -1, *([b.data_ptr() for b in bufs] + [None])) == N.FSQ_EINVAL
+    assert NP.lib().fsq_peptide_simulate(ctypes.byref(_prm(BASE, 1, 2 ** 63 - 5)), n, *([b.data_ptr() for b in bufs] + [None])) == N.FSQ_EINVAL
+
+
+CHAIN = dict(p=0.9, b=-math.log(1.0 - 0.1), u=0.5, s=0.3, sc=3, s2=0.1, beta=70000.0, beta_sigma=0.2, ddif=[0, 0.3] + [0.3] * 5,
+             superdye_rate=0.0, superdye_factor=1.0)
+
+
+def test_simulate_and_fit_records_equals_the_twin_through_the_fit():
+    from fluorosequencingimageanalysis_amd import lognormal as LN
+    from fluorosequencingimageanalysis_amd import peptide_simulator as PS
+    seq, label, n, seed = "GAKAGAKC", "K", 4096, 777
+    with _prefilled():
+        out = PS.simulate_and_fit_records(seq, label, 3, 8, n, seed=seed, max_possible=5, allow_multidrop=True, max_deviation=3,
+                                          quench_factors=CHAIN["ddif"], **CHAIN)
+    mask = sum(1 << i for i, ch in enumerate(seq) if ch == label)
+    rec = T.simulate(len(seq), mask, 3, 8, 0.9, math.e ** -CHAIN["b"], 0.5, 0.3, 3, 0.1, math.log(70000.0), 0.2, CHAIN["ddif"], 0.0, 1.0,
+                     seed, 0, n)
+    same_records({k: v.cpu().numpy() for k, v in out["simulation"].items() if hasattr(v, "cpu")}, rec)
+    photometries, mes, t = {'ch1': {0: {}}}, {}, 0
+    for counts, inten in zip(rec["counts"].tolist(), rec["intensity"].tolist()):
+        if not any(counts):
+            continue
+        photometries['ch1'][0][(t, t)] = (tuple(c > 0 for c in counts), tuple(inten), t)
+        t += 1
+        dec = tuple(('A', f) for f in range(1, len(counts)) for _ in range(counts[f - 1] - counts[f])) or (('A', 0),)
+        key = (dec, counts[-1] == 0, counts[0])
+        mes[key] = mes.get(key, 0) + 1
+    signals, total, none_count, _ = LN.photometries_lognormal_fit(photometries, 70000.0, 0.2, max_possible=5, allow_multidrop=True,
+                                                                  max_deviation=3, quench_factor=0, quench_factors=CHAIN["ddif"])
+    assert out["signals"] == signals and out["total_count"] == total == t and out["none_count"] == none_count
+    assert out["molecular_error_signals"] == mes
+    assert len(signals) > 20 and len(mes) > 20 and 0 < none_count < total and int(out["kept"].sum()) == t
+
+
+def test_command_line_on_the_device_equals_the_twin(tmp_path):
+    from fluorosequencingimageanalysis_amd import simulate_peptide as SP
+    common = ["KAGKAGC", "K", "-N", "500", "--seed", "123456789", "--superdye_rate", "0.25", "--superdye_factor", "2.0"]
+    dev = SP.main(common + ["--output_directory", str(tmp_path / "dev")])
+    host = SP.main(common + ["--host", "--output_directory", str(tmp_path / "host")])
+    a, b = pickle.load(open(dev, "rb")), pickle.load(open(host, "rb"))
+    assert a[1] == b[1] and a[2] == b[2] and len(a[1]) > 5 and len(a[2]) > 5
+    da, db = vars(a[0]), vars(b[0])
+    assert {k: v for k, v in da.items() if k not in ("host", "output_directory")} == {k: v for k, v in db.items() if k not in ("host", "output_directory")}
+    assert open(dev[:-4] + ".csv", newline='').read() == open(host[:-4] + ".csv", newline='').read()
+    assert os.path.getsize(dev[:-4] + ".csv") > 10000
