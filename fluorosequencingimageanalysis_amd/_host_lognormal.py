@@ -1,5 +1,6 @@
 """Plain Python / NumPy restatement of MCsimlib._intensities_to_signal_lognormal_v8 (:5413-5493, allow_upsteps=False): the
-checker of the lognormal tests, pinned to the reference's recorded outputs by tests/test_lognormal_host.py.
+fit of `simulate_peptide --host` and the checker of the device fit, pinned to the reference's recorded outputs by
+test_lognormal_host.
 
 The reference enumerates every non-increasing count sequence and skips the ones that break a rule; this walks the same
 sequences depth-first in the same order (largest count first) and leaves a branch at the first frame that breaks the

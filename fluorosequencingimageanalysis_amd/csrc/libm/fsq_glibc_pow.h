@@ -1,67 +1,15 @@
 // fsq_glibc_pow.h - pow(x, 2.0) and pow(x, -2.0) as glibc 2.35 computes them (e_pow.c, FMA variant), shared by the
-// step-fit kernels (fsq_stepfit.hip, fsq_chisq.hip).  Include after ../fsq_devmath.h.
+// step-fit kernels (fsq_stepfit.hip, fsq_chisq.hip) and the bin search (fsq_binsearch.hip).  Include after ../fsq_devmath.h.
 // fsq_devmath.h keeps its own fsq_pow2 for the fit engine and consolidation: that file is part of the hashed kernel sources.
 #pragma once
 
+#include "fsq_glibc_exp.h"
+
 namespace {
-
-// fsq_exp_special / fsq_exp_core<true> of fsq_devmath.h, force-inlined: a kernel that makes no call needs no scratch frame
-__device__ __forceinline__ double sf_exp_special(double tmp, unsigned long long sbits, unsigned long long ki)
-{
-    double scale, y;
-    if ((ki & 0x80000000ull) == 0) {
-        sbits -= 1009ull << 52;
-        scale = fsq_dbl(sbits);
-        return 0x1p1009 * fsq_fma(scale, tmp, scale);
-    }
-    sbits += 1022ull << 52;
-    scale = fsq_dbl(sbits);
-    y = scale + scale * tmp;
-    if (y < 1.0) {
-        double hi, lo;
-        lo = scale - y + scale * tmp;
-        hi = 1.0 + y;
-        lo = 1.0 - hi + y + lo;
-        y = (hi + lo) - 1.0;
-        if (y == 0.0) y = 0.0;
-    }
-    return 0x1p-1022 * y;
-}
-
-__device__ __forceinline__ double sf_exp_pow(double x, double xtail)
-{
-    unsigned abstop = (unsigned)(fsq_bits(x) >> 52) & 0x7ff;
-    if (__builtin_expect(abstop - 0x3c9u >= 0x3fu, 0)) {
-        if (abstop - 0x3c9u >= 0x80000000u) return 1.0 + x;
-        if (abstop >= 0x409u) {
-            return (fsq_bits(x) >> 63) ? 0.0 : __builtin_inf();   // __math_uflow / __math_oflow values
-        }
-        abstop = 0;
-    }
-    double kd = fsq_fma(x, EXP_INVLN2N, EXP_SHIFT);
-    unsigned long long ki = fsq_bits(kd);
-    kd -= EXP_SHIFT;
-    double r = fsq_fma(kd, EXP_NEGLN2HIN, x);
-    r = fsq_fma(kd, EXP_NEGLN2LON, r);
-    r = xtail + r;
-    unsigned idx = 2u * ((unsigned)ki & 127u);
-    unsigned long long top = ki << 45;
-    double tail = fsq_dbl(FSQ_EXP_TAB[idx]);
-    unsigned long long sbits = FSQ_EXP_TAB[idx + 1] + top;
-    double r2 = r * r;
-    double p23 = fsq_fma(EXP_C3, r, EXP_C2);
-    double p45 = fsq_fma(r, EXP_C5, EXP_C4);
-    double t = r + tail;
-    double tmp = fsq_fma(p23, r2, t);
-    tmp = fsq_fma(r2 * r2, p45, tmp);
-    if (__builtin_expect(abstop == 0, 0)) return sf_exp_special(tmp, sbits, ki);
-    double scale = fsq_dbl(sbits);
-    return fsq_fma(scale, tmp, scale);
-}
 
 // pow(x, Y) for Y = 2 or -2.  Negative bases drop their sign (Y is even); 0 / inf / nan give x * x for Y = 2 and
 // +inf (__math_divzero) or 1 / (x * x) for Y = -2; tiny results go through exp's specialcase.  INLINE_EXP chooses the
-// force-inlined exp tail above over fsq_devmath.h's fsq_exp_core<true>, which calls fsq_exp_special.
+// force-inlined exp of fsq_glibc_exp.h over fsq_devmath.h's fsq_exp_core<true>, which calls fsq_exp_special.
 template <int Y, bool INLINE_EXP>
 __device__ __forceinline__ double sf_pow(double x)
 {
@@ -112,7 +60,7 @@ __device__ __forceinline__ double sf_pow(double x)
     const double Yd = (double)Y;
     double ehi = Yd * y;                                               // y * hi, y * lo + fma(y, hi, -ehi) of e_pow.c
     double elo = fsq_fma(Yd, tail, fsq_fma(y, Yd, -ehi));
-    return INLINE_EXP ? sf_exp_pow(ehi, elo) : fsq_exp_core<true>(ehi, elo);
+    return INLINE_EXP ? sf_exp<true>(ehi, elo) : fsq_exp_core<true>(ehi, elo);
 }
 
 }  // namespace

@@ -10,7 +10,7 @@
 //      are left; the thread whose remaining bits are zero owns that leaf and sums it with numpy's 8 accumulators straight
 //      from the ranks.  Seven barrier-separated steps then add each right child to its left sibling, deepest level first;
 //   4. thread 0 adds the chunk sums left to right and writes the cost; its divisor is glibc's pow(step, 2.0)
-//      (stepfit/fsq_glibc_pow.h), which is what the reference's `bin_size**2` on a numpy scalar calls.
+//      (libm/fsq_glibc_pow.h), which is what the reference's `bin_size**2` on a numpy scalar calls.
 // Every LDS index is below nb + 1 <= FSQ_BINSEARCH_MAX_BINS + 1 and every global index below n; a bin count outside
 // 1 .. FSQ_BINSEARCH_MAX_BINS leaves NaN and touches nothing else.
 // kbs_costs<true> (fsq_histogram_costs_sorted) reads lo and hi from sorted[0] and sorted[n - 1] instead of taking them from
@@ -20,7 +20,7 @@
 
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
-#include "../stepfit/fsq_glibc_pow.h"
+#include "../libm/fsq_glibc_pow.h"
 #include "../stepfit/fsq_pairwise.h"
 #include "../../../include/fsq_binsearch.h"
 

@@ -17,7 +17,8 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_lognormal.h"
-#include "fsq_glibc_log.h"
+#include "../libm/fsq_glibc_exp.h"
+#include "../libm/fsq_glibc_log.h"
 
 namespace {
 
@@ -25,60 +26,6 @@ constexpr int WAVE = 64;
 constexpr int MAX_BLOCKS = 16384;
 constexpr unsigned long long SAT = (unsigned long long)FSQ_LOGNORMAL_MAX_BUDGET;
 constexpr double NORM_PDF_C = 0x1.40d931ff62705p+1;          // np.sqrt(2 * np.pi), scipy's _norm_pdf_C
-
-// fsq_exp of fsq_devmath.h with specialcase() force-inlined: a kernel that makes no call needs no scratch frame
-// (fsq_devmath.h is among the hashed kernel sources and stays as it is; the "subnormal" cases of
-// tests/golden/lognormal_tracks.npz pin this copy's special-case tail)
-__device__ __forceinline__ double ln_exp(double x)
-{
-    unsigned abstop = (unsigned)(fsq_bits(x) >> 52) & 0x7ff;
-    if (__builtin_expect(abstop - 0x3c9u >= 0x3fu, 0)) {
-        if (abstop - 0x3c9u >= 0x80000000u) return 1.0 + x;
-        if (abstop >= 0x409u) {
-            if (fsq_bits(x) == 0xfff0000000000000ull) return 0.0;
-            if (abstop >= 0x7ffu) return 1.0 + x;
-            return (fsq_bits(x) >> 63) ? 0.0 : __builtin_inf();
-        }
-        abstop = 0;
-    }
-    double kd = fsq_fma(x, EXP_INVLN2N, EXP_SHIFT);
-    unsigned long long ki = fsq_bits(kd);
-    kd -= EXP_SHIFT;
-    double r = fsq_fma(kd, EXP_NEGLN2HIN, x);
-    r = fsq_fma(kd, EXP_NEGLN2LON, r);
-    unsigned idx = 2u * ((unsigned)ki & 127u);
-    unsigned long long top = ki << 45;
-    double tail = fsq_dbl(FSQ_EXP_TAB[idx]);
-    unsigned long long sbits = FSQ_EXP_TAB[idx + 1] + top;
-    double r2 = r * r;
-    double p23 = fsq_fma(EXP_C3, r, EXP_C2);
-    double p45 = fsq_fma(r, EXP_C5, EXP_C4);
-    double t = r + tail;
-    double tmp = fsq_fma(p23, r2, t);
-    tmp = fsq_fma(r2 * r2, p45, tmp);
-    if (__builtin_expect(abstop == 0, 0)) {
-        double scale, y;
-        if ((ki & 0x80000000ull) == 0) {
-            sbits -= 1009ull << 52;
-            scale = fsq_dbl(sbits);
-            return 0x1p1009 * fsq_fma(scale, tmp, scale);
-        }
-        sbits += 1022ull << 52;
-        scale = fsq_dbl(sbits);
-        y = scale + scale * tmp;
-        if (y < 1.0) {
-            double hi, lo;
-            lo = scale - y + scale * tmp;
-            hi = 1.0 + y;
-            lo = 1.0 - hi + y + lo;
-            y = (hi + lo) - 1.0;
-            if (y == 0.0) y = 0.0;
-        }
-        return 0x1p-1022 * y;
-    }
-    double scale = fsq_dbl(sbits);
-    return fsq_fma(scale, tmp, scale);
-}
 
 // The counts of one sequence, 4 bits per frame, in one register vector (an indexed array or struct would live in scratch).
 typedef unsigned long long Seq __attribute__((ext_vector_type(4)));
@@ -158,7 +105,7 @@ __global__ void __launch_bounds__(WAVE) kln_fit(const double* __restrict__ inten
                     const double d = Lf[f] - Mn[v - 1];
                     const double z = d / prm.beta_sigma;
                     adm = on && !(__builtin_fabs(d) / prm.beta_sigma > prm.max_deviation);
-                    s = ln_exp(-(z * z) / 2.0) / NORM_PDF_C / prm.beta_sigma;
+                    s = sf_exp<false>(-(z * z) / 2.0, 0.0) / NORM_PDF_C / prm.beta_sigma;
                 }
                 S[idx] = s;
                 W[idx] = adm ? 1ull : 0ull;

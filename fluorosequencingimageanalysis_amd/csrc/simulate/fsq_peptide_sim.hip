@@ -14,7 +14,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_peptide_sim.h"
-#include "../lognormal/fsq_glibc_log.h"
+#include "../libm/fsq_glibc_log.h"
 
 namespace {
 

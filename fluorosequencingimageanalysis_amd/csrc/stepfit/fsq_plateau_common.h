@@ -3,7 +3,7 @@
 #pragma once
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_stepfit.h"
-#include "fsq_glibc_pow.h"
+#include "../libm/fsq_glibc_pow.h"
 
 namespace {
 

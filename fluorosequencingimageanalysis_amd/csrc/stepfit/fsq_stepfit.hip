@@ -13,7 +13,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_stepfit.h"
-#include "fsq_glibc_pow.h"
+#include "../libm/fsq_glibc_pow.h"
 #include "fsq_pairwise.h"
 
 namespace {

@@ -22,6 +22,25 @@ def _torch():
     return torch
 
 
+def launch(fn, what, dev, *args):
+    """One entry of the C ABI on the tensors' device: makes `dev` current for the call (the entries set no device themselves),
+    passes torch's current stream of `dev` as the last argument and raises for the return code under the name `what`."""
+    import torch                    # (the caller holds tensors on `dev`: no need to ask again whether there is a GPU)
+    with torch.cuda.device(dev):
+        N.check(fn(*args, torch.cuda.current_stream(dev).cuda_stream), what)
+
+
+def workspace(dev, n_bytes):
+    """A launch's workspace of n_bytes on `dev`: int64 words (8-byte aligned), at least one."""
+    import torch
+    return torch.empty(max((int(n_bytes) + 7) // 8, 1), dtype=torch.int64, device=dev)
+
+
+def to_host(out):
+    """A dict of device tensors as NumPy arrays; keys that start with '_' (what a launch keeps alive) are left out."""
+    return {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+
+
 def to_device_u16(images, device=None):
     """uint16 numpy array (any shape; or the 16-bit words of a float16 image, as_pixel_fields) -> int16-typed torch
     tensor on the GPU holding the same bytes."""

@@ -25,10 +25,6 @@ from . import sequencing as _sq
 CANDIDATE_RADIUS, SPOT_RADIUS = 2, 0            # SequenceExperiment.trace_existing_spots' arguments (flexlibrary.py:1770-1809)
 
 
-def _stream(torch, dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def spot_table_device(d_records, d_peaks, H, W, spot_size=NX.SPOT_SIZE):
     """fsq_experiment_spot_table on device tensors: d_records uint8 [k, 378 | 428], d_peaks int32 [n_frames].  -> dict of device
     tensors hw int32 [k, 2], spot_record int32 [k] (the first n_spots rows are written), counts, discarded, status int32
@@ -44,12 +40,11 @@ def spot_table_device(d_records, d_peaks, H, W, spot_size=NX.SPOT_SIZE):
     out = {"hw": torch.empty((max(k, 1), 2), **i32), "spot_record": torch.empty(max(k, 1), **i32),
            "counts": torch.empty(max(n_frames, 1), **i32), "discarded": torch.empty(max(n_frames, 1), **i32),
            "status": torch.empty(max(n_frames, 1), **i32), "n_spots": torch.empty(1, **i32)}
-    ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dev)
-    rc = L.fsq_experiment_spot_table(d_records.data_ptr() if k else None, k, int(d_records.shape[1]), d_peaks.data_ptr(), n_frames,
-                                     int(H), int(W), int(spot_size), out["hw"].data_ptr(), out["spot_record"].data_ptr(),
-                                     out["counts"].data_ptr(), out["discarded"].data_ptr(), out["status"].data_ptr(),
-                                     out["n_spots"].data_ptr(), ws.data_ptr(), int(ws_bytes), _stream(torch, dev))
-    N.check(rc, "fsq_experiment_spot_table")
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_experiment_spot_table, "fsq_experiment_spot_table", dev, d_records.data_ptr() if k else None, k,
+                   int(d_records.shape[1]), d_peaks.data_ptr(), n_frames, int(H), int(W), int(spot_size), out["hw"].data_ptr(),
+                   out["spot_record"].data_ptr(), out["counts"].data_ptr(), out["discarded"].data_ptr(), out["status"].data_ptr(),
+                   out["n_spots"].data_ptr(), ws.data_ptr(), int(ws_bytes))
     out["hw"], out["spot_record"] = out["hw"][:k], out["spot_record"][:k]
     for name in ("counts", "discarded", "status"):
         out[name] = out[name][:n_frames]
@@ -62,8 +57,8 @@ def trace_starts_device(d_n_traces):
     torch = _engine._torch()
     n_seq = int(d_n_traces.shape[0])
     d_start = torch.empty(n_seq + 1, dtype=torch.int32, device=d_n_traces.device)
-    N.check(NX.lib().fsq_experiment_trace_starts(d_n_traces.data_ptr() if n_seq else None, n_seq, d_start.data_ptr(),
-                                                 _stream(torch, d_n_traces.device)), "fsq_experiment_trace_starts")
+    _engine.launch(NX.lib().fsq_experiment_trace_starts, "fsq_experiment_trace_starts", d_n_traces.device,
+                   d_n_traces.data_ptr() if n_seq else None, n_seq, d_start.data_ptr())
     return d_start
 
 
@@ -75,9 +70,8 @@ def trace_rows_device(d_traces, d_seq_start, d_field_start, d_hw, n_frames, n_ro
     n_seq, F, n = int(d_seq_start.shape[0]) - 1, int(n_frames), int(n_rows)
     i32 = dict(dtype=torch.int32, device=dev)
     t_hw, t_spot, t_seq = torch.empty((max(n, 1), F, 2), **i32), torch.empty((max(n, 1), F), **i32), torch.empty(max(n, 1), **i32)
-    rc = NX.lib().fsq_experiment_trace_rows(d_traces.data_ptr(), d_seq_start.data_ptr(), d_field_start.data_ptr(), d_hw.data_ptr(),
-                                            n_seq, F, n, t_hw.data_ptr(), t_spot.data_ptr(), t_seq.data_ptr(), _stream(torch, dev))
-    N.check(rc, "fsq_experiment_trace_rows")
+    _engine.launch(NX.lib().fsq_experiment_trace_rows, "fsq_experiment_trace_rows", dev, d_traces.data_ptr(), d_seq_start.data_ptr(),
+                   d_field_start.data_ptr(), d_hw.data_ptr(), n_seq, F, n, t_hw.data_ptr(), t_spot.data_ptr(), t_seq.data_ptr())
     return t_hw[:n], t_spot[:n], t_seq[:n]
 
 
@@ -158,12 +152,11 @@ def _track_device(torch, dev, d_hw, d_field_start, d_counts, d_off, n_seq, F, H,
         ws_bytes = L.fsq_track_workspace_bytes(n_seq, F, H, W, pair_cap)
         if ws_bytes < 0:
             raise ValueError("invalid tracking shape")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        rc = L.fsq_greedy_tracking(d_hw.data_ptr(), d_field_start.data_ptr(), d_counts.data_ptr(), d_off.data_ptr(), n_seq, F, H, W,
-                                   CANDIDATE_RADIUS, float(SPOT_RADIUS), d_prev.data_ptr(), d_next.data_ptr(), d_kept.data_ptr(),
-                                   d_traces.data_ptr(), d_nt.data_ptr(), d_nd.data_ptr(), d_st.data_ptr(), pair_cap, ws.data_ptr(),
-                                   ws_bytes, _stream(torch, dev))
-        N.check(rc, "fsq_greedy_tracking")
+        ws = _engine.workspace(dev, ws_bytes)
+        _engine.launch(L.fsq_greedy_tracking, "fsq_greedy_tracking", dev, d_hw.data_ptr(), d_field_start.data_ptr(), d_counts.data_ptr(),
+                       d_off.data_ptr(), n_seq, F, H, W, CANDIDATE_RADIUS, float(SPOT_RADIUS), d_prev.data_ptr(), d_next.data_ptr(),
+                       d_kept.data_ptr(), d_traces.data_ptr(), d_nt.data_ptr(), d_nd.data_ptr(), d_st.data_ptr(), pair_cap, ws.data_ptr(),
+                       ws_bytes)
         # (a sequence that failed has no traces: its count is not read)
         d_start = trace_starts_device(torch.where(d_st == 0, d_nt, torch.zeros_like(d_nt)))
         word = torch.cat([d_st, d_start[-1:]]).cpu().numpy()
@@ -354,7 +347,7 @@ def sequence_experiment_records(frames, alignment_frames=None, self_align=True, 
         dev_out = {"offsets": d_off, "n_dropouts": d_nd, "seq_start": d_seq_start, "spot_hw": d_hw, "spot_record": d_spot_record,
                    "trace_hw": d_trace_hw, "trace_spot": d_trace_spot, "trace_seq": d_trace_seq, "hw": o["hw"], "photometry": d_phot,
                    "flags": o["flags"], "category": o["category"], "trace_valid": o["trace_valid"]}
-        host = {k: v.cpu().numpy() for k, v in dev_out.items()}
+        host = _engine.to_host(dev_out)
         host["counts"] = _sq._counts_to_host(*all_counts[:5])
         host["filtered_counts"] = _sq._counts_to_host(*kept_counts[:5])
         mark("download")

@@ -25,10 +25,11 @@ from math import log, sqrt
 
 import numpy as np
 
-from . import _native as N
 from . import _native_binsearch as NB
 from . import _native_lognormal as NL
+from . import _tracks
 from . import engine as _engine
+from ._tracks import category_word                                # noqa: F401  (its old place)
 from .pflib import _py2_round
 
 STATUS_FOUND, STATUS_NONE, STATUS_OVER_BUDGET = NL.STATUS_FOUND, NL.STATUS_NONE, NL.STATUS_OVER_BUDGET
@@ -43,7 +44,7 @@ def _no_upsteps(allow_upsteps):
         raise NotImplementedError("allow_upsteps=True is not built")
 
 
-def _params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget):
+def fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget):
     """FsqLognormalParams after the checks the module docstring names."""
     if log_fluor_means is None:
         raise ValueError("v8+ requires log_fluor_means to be passed manually")
@@ -79,10 +80,10 @@ def lognormal_device(d_intensity, d_category, d_len, log_fluor_means, beta_sigma
     is ON, the uint64 word of sequencing.py) and int32 [n] lengths.  Returns a dict of device tensors: status int32 [n], best_seq
     uint8 [n, max_frames], best_score float64 [n], frame_score float64 [n, max_frames], n_surviving int64 [n].  Enqueued on the
     current stream, not synchronised.  Lengths and intensities are not checked here: a track whose length is not in
-    1 .. max_frames comes back with status 3.  `prm`: the parameters already built by _params (the other arguments are then unused)."""
+    1 .. max_frames comes back with status 3.  `prm`: the parameters already built by fit_params (the other arguments are then unused)."""
     torch = _engine._torch()
     if prm is None:
-        prm = _params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
+        prm = fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
     dev = d_intensity.device
     n, max_frames = int(d_intensity.shape[0]), int(d_intensity.shape[1])
     if max_frames > NL.MAX_FRAMES:
@@ -100,11 +101,9 @@ def lognormal_device(d_intensity, d_category, d_len, log_fluor_means, beta_sigma
            "best_score": torch.empty(n, dtype=torch.float64, device=dev),
            "frame_score": torch.empty((n, max_frames), dtype=torch.float64, device=dev),
            "n_surviving": torch.empty(n, dtype=torch.int64, device=dev)}
-    rc = L.fsq_lognormal_fit(d_intensity.data_ptr(), d_category.data_ptr(), d_len.data_ptr(), n, max_frames, ctypes.byref(prm),
-                             out["status"].data_ptr(), out["best_seq"].data_ptr(), out["best_score"].data_ptr(),
-                             out["frame_score"].data_ptr(), out["n_surviving"].data_ptr(), None, 0,
-                             torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_lognormal_fit")
+    _engine.launch(L.fsq_lognormal_fit, "fsq_lognormal_fit", dev, d_intensity.data_ptr(), d_category.data_ptr(), d_len.data_ptr(), n,
+                   max_frames, ctypes.byref(prm), out["status"].data_ptr(), out["best_seq"].data_ptr(), out["best_score"].data_ptr(),
+                   out["frame_score"].data_ptr(), out["n_surviving"].data_ptr(), None, 0)
     return out
 
 
@@ -114,40 +113,23 @@ def log_device(d_x):
     if d_x.dtype != torch.float64 or not d_x.is_contiguous():
         raise ValueError("a contiguous float64 tensor is needed")
     out = torch.empty_like(d_x)
-    N.check(NL.lib().fsq_lognormal_log(d_x.data_ptr(), out.data_ptr(), int(d_x.numel()),
-                                       torch.cuda.current_stream(d_x.device).cuda_stream), "fsq_lognormal_log")
+    _engine.launch(NL.lib().fsq_lognormal_log, "fsq_lognormal_log", d_x.device, d_x.data_ptr(), out.data_ptr(), int(d_x.numel()))
     return out
-
-
-def category_word(category):
-    """A tuple of booleans as the uint64 word: bit f set when frame f is ON."""
-    return sum(1 << f for f, c in enumerate(category) if c)
 
 
 def _rows(intensities, categories, lengths):
     """(float64 [n, max_frames], uint64 [n], int32 [n]) of ragged host sequences, or of a 2-D array with lengths."""
-    if isinstance(intensities, np.ndarray) and intensities.ndim == 2:
-        rows = np.ascontiguousarray(intensities, dtype=np.float64)
-        lens = (np.full(len(rows), rows.shape[1], np.int32) if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32))
-    else:
-        seqs = [np.asarray(s, dtype=np.float64).reshape(-1) for s in intensities]
-        lens = np.array([len(s) for s in seqs], dtype=np.int32)
-        rows = np.zeros((len(seqs), max(int(lens.max()), 1) if len(seqs) else 1), dtype=np.float64)
-        for i, s in enumerate(seqs):
-            rows[i, :len(s)] = s
-    if len(lens) and lens.min() < 1:
-        raise ValueError("max() arg is an empty sequence")        # (max(intensities) of a track without frames, :5413)
+    rows, lens = _tracks.pack_rows(intensities, lengths, min_frames=1,
+                                   short_error="max() arg is an empty sequence")   # (max(intensities) of a track without frames, :5413)
     if len(lens) and lens.max() > rows.shape[1]:
         raise ValueError("a length exceeds the width of the rows")
     if len(lens) and lens.max() > NL.MAX_FRAMES:
         raise NotImplementedError("tracks are limited to %d frames" % NL.MAX_FRAMES)
-    if isinstance(categories, np.ndarray) and categories.ndim == 1 and categories.dtype.kind in "iu":
-        cats = np.ascontiguousarray(categories).astype(np.uint64)
-    else:
-        for i, c in enumerate(categories):
-            if i < len(lens) and len(c) < lens[i]:
-                raise IndexError("tuple index out of range")      # (categories[i] of a frame beyond the category, :5436)
-        cats = np.array([category_word(c[:NL.MAX_FRAMES]) for c in categories], dtype=np.uint64)
+    if not (isinstance(categories, np.ndarray) and categories.ndim == 1 and categories.dtype.kind in "iu"):
+        categories = list(categories)
+        if any(len(c) < T for c, T in zip(categories, lens)):
+            raise IndexError("tuple index out of range")          # (categories[i] of a frame beyond the category, :5436)
+    cats = _tracks.category_words(categories, None)
     if not (len(rows) == len(cats) == len(lens)):
         raise ValueError("one category and one length per track")
     valid = np.arange(rows.shape[1])[None, :] < lens[:, None]
@@ -165,7 +147,7 @@ def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_
     Returns a dict of NumPy arrays: status (STATUS_FOUND / STATUS_NONE / STATUS_OVER_BUDGET), best_seq uint8 [n, max_frames],
     best_score, frame_score [n, max_frames], n_surviving int64 and lengths.  Rows beyond a track's length, and the rows of
     a track without a winner, hold count 0, score 0 and best_score -1."""
-    prm = _params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
+    prm = fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
     if hasattr(intensities, "is_cuda"):                            # a torch tensor
         torch = _engine._torch()
         d_int = intensities.contiguous()
@@ -193,7 +175,7 @@ def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_
         return {"status": np.zeros(0, np.int32), "best_seq": np.zeros((0, 1), np.uint8), "best_score": np.zeros(0),
                 "frame_score": np.zeros((0, 1)), "n_surviving": np.zeros(0, np.int64), "lengths": np.zeros(0, np.int32)}
     out = lognormal_device(d_int, d_cat, d_len, None, None, prm=prm)
-    host = {k: v.cpu().numpy() for k, v in out.items()}
+    host = _engine.to_host(out)
     host["lengths"] = np.asarray(lens, dtype=np.int32)
     return host
 
@@ -257,15 +239,9 @@ def histogram_costs_device(d_values, bin_counts, lo=None, hi=None):
     else:
         d_counts = torch.from_numpy(_checked_bin_counts(bin_counts)).to(dev)
     d_cost = torch.empty(int(d_counts.numel()), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if lo is None:
-            rc = NB.lib().fsq_histogram_costs_sorted(d_sorted.data_ptr(), int(d_sorted.numel()), d_counts.data_ptr(),
-                                                     int(d_counts.numel()), d_cost.data_ptr(), stream)
-        else:
-            rc = NB.lib().fsq_histogram_costs(d_sorted.data_ptr(), int(d_sorted.numel()), float(lo), float(hi), d_counts.data_ptr(),
-                                              int(d_counts.numel()), d_cost.data_ptr(), stream)
-    N.check(rc, "fsq_histogram_costs")
+    bounds = () if lo is None else (float(lo), float(hi))
+    _engine.launch(NB.lib().fsq_histogram_costs_sorted if lo is None else NB.lib().fsq_histogram_costs, "fsq_histogram_costs", dev,
+                   d_sorted.data_ptr(), int(d_sorted.numel()), *bounds, d_counts.data_ptr(), int(d_counts.numel()), d_cost.data_ptr())
     return d_cost
 
 
@@ -283,10 +259,8 @@ def histogram_counts_device(d_values, n_bins, lo=None, hi=None):
     lo, hi = float(lo), float(hi)
     dev = d_sorted.device
     d_hist = torch.empty(n_bins, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = NB.lib().fsq_histogram_counts(d_sorted.data_ptr(), int(d_sorted.numel()), lo, hi, n_bins, d_hist.data_ptr(),
-                                           torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_histogram_counts")
+    _engine.launch(NB.lib().fsq_histogram_counts, "fsq_histogram_counts", dev, d_sorted.data_ptr(), int(d_sorted.numel()), lo, hi,
+                   n_bins, d_hist.data_ptr())
     return d_hist
 
 
@@ -319,7 +293,7 @@ def histogram_counts(values, n_bins, device=None):
 
 # ---- the reference's call surface ----
 
-def _signal(best_seq):
+def signal_of(best_seq):
     """(signal, is_zero, starting_intensity) of a winning sequence (:5467-5491)."""
     drops = [best_seq[f] - fc for f, fc in enumerate(best_seq[1:])]
     signal = []
@@ -345,7 +319,7 @@ def _fit_tuples(host, max_possible, what):
     for st, seq, fs, score, T in zip(status.tolist(), seqs, fscores, scores, lens):
         if st == STATUS_FOUND:
             best_seq = tuple(seq[:T])
-            signal, is_zero, start = _signal(best_seq)
+            signal, is_zero, start = signal_of(best_seq)
             out.append((signal, is_zero, best_seq, max_possible, score, fs[:T], start))
         else:
             out.append((None, None, None, max_possible, -1, None, None))
@@ -404,9 +378,7 @@ def photometries_lognormal_fit(photometries, beta, beta_sigma, max_possible=5, n
     accepted and unused.  A track over `budget` raises NotImplementedError naming it."""
     if len(photometries) > 1:
         raise NotImplementedError("Currently puts all photometries together, can't handle multiple channels at once.")
-    if quench_factors is None or len(quench_factors) != max_possible + 2:
-        raise ValueError("quench_factors required for v8+")
-    log_fluor_means = [log(beta) + log(i + 1.0) - quench_factors[i] for i in range(max_possible + 2)]
+    log_fluor_means = _tracks.log_fluor_means(beta, quench_factors, max_possible)
     tracks = list(unwind_photometries(photometries))
     _no_upsteps(allow_upsteps)
     if not allow_multidrop and any(len(t[5]) == 1 for t in tracks):
@@ -414,15 +386,9 @@ def photometries_lognormal_fit(photometries, beta, beta_sigma, max_possible=5, n
     host = lognormal_records([t[5] for t in tracks], [t[4] for t in tracks], log_fluor_means, beta_sigma, max_possible,
                              allow_multidrop, max_deviation, budget, device=device)
     fits = _fit_tuples(host, max_possible, lambda i: "track %s field %s (%s, %s)" % tracks[i][:4])
-    signals, none_count, all_fit_info = {}, 0, []
-    for (channel, field, h, w, category, intensities, row), fit in zip(tracks, fits):
-        signal, is_zero, best_seq, lmii, best_score, best_intensity_scores, starting_intensity = fit
-        all_fit_info.append((channel, field, h, w, row, category, intensities) + fit)
-        if signal is None:
-            none_count += 1
-        else:
-            key = (signal, is_zero, starting_intensity)
-            signals[key] = signals.get(key, 0) + 1
+    all_fit_info = [(channel, field, h, w, row, category, intensities) + fit
+                    for (channel, field, h, w, category, intensities, row), fit in zip(tracks, fits)]
+    signals, none_count = _tracks.tally_signals((f[0], f[1], f[6]) for f in fits)
     return signals, len(tracks), none_count, all_fit_info
 
 

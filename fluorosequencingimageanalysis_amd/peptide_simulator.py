@@ -24,8 +24,9 @@ from string import ascii_letters, digits
 
 import numpy as np
 
-from . import _native as N
+from . import _host_peptide_sim
 from . import _native_peptide_sim as NP
+from . import _tracks
 from . import engine as _engine
 
 FluorEvent = namedtuple('FluorEvent', ['original_position', 'original_amino_acid', 'event_name', 'cycle_number', 'message'])
@@ -111,10 +112,8 @@ def philox_words_device(d_counters, d_keys):
         raise ValueError("int32 tensors [n, 4] and [n, 2] are needed")
     d_counters, d_keys = d_counters.contiguous(), d_keys.contiguous()
     out = torch.empty((n, 4), dtype=torch.int32, device=d_counters.device)
-    with torch.cuda.device(d_counters.device):
-        rc = NP.lib().fsq_philox_words(d_counters.data_ptr(), d_keys.data_ptr(), n, out.data_ptr(),
-                                       torch.cuda.current_stream(d_counters.device).cuda_stream)
-    N.check(rc, "fsq_philox_words")
+    _engine.launch(NP.lib().fsq_philox_words, "fsq_philox_words", d_counters.device, d_counters.data_ptr(), d_keys.data_ptr(), n,
+                   out.data_ptr())
     return out
 
 
@@ -135,10 +134,8 @@ def simulate_device_prm(prm, n_molecules, device=None):
            "log_intensity": torch.empty((n, F), dtype=torch.float64, device=dev),
            "category": torch.empty(n, dtype=torch.int64, device=dev),
            "n_draws": torch.empty((n, 3), dtype=torch.int32, device=dev)}
-    with torch.cuda.device(dev):
-        rc = NP.lib().fsq_peptide_simulate(ctypes.byref(prm), n, *([out[k].data_ptr() if out[k].numel() else None for k in TABLES] +
-                                                                  [torch.cuda.current_stream(dev).cuda_stream]))
-    N.check(rc, "fsq_peptide_simulate")
+    _engine.launch(NP.lib().fsq_peptide_simulate, "fsq_peptide_simulate", dev, ctypes.byref(prm), n,
+                   *[out[k].data_ptr() if out[k].numel() else None for k in TABLES])
     return out
 
 
@@ -156,30 +153,17 @@ def simulate_device(sequence, labels, num_mocks, num_edmans, num_simulations=1, 
     return out
 
 
-def _host_twin():
-    """tests/_peptide_sim_reference.py of the source tree: the NumPy twin of the kernel."""
-    import importlib.util
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "_peptide_sim_reference.py")
-    if not os.path.exists(path):
-        raise RuntimeError("%s not found: the host twin lives in the source tree" % path)
-    spec = importlib.util.spec_from_file_location("_peptide_sim_reference", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def simulation_records(sequence, labels, num_mocks, num_edmans, num_simulations=1, seed=0, first_molecule=0, device=None,
                        host=False, **experimental_parameters):
     """simulate_device's dict as NumPy arrays (edman_fail and category as uint64).  host=True: the same records from the
     NumPy twin of the kernel, without a GPU."""
     prm, meta = _params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, experimental_parameters)
     if host:
-        T = _host_twin()
-        out = T.simulate(prm.length, prm.label_mask, prm.num_mocks, prm.num_edmans, prm.p, prm.per_cycle_b, prm.u, prm.s, prm.sc,
-                         prm.s2, prm.log_beta, prm.beta_sigma, list(prm.ddif)[:prm.n_ddif], prm.superdye_rate, prm.superdye_factor,
-                         prm.seed, prm.first_molecule, int(num_simulations))
+        out = _host_peptide_sim.simulate(prm.length, prm.label_mask, prm.num_mocks, prm.num_edmans, prm.p, prm.per_cycle_b, prm.u,
+                                         prm.s, prm.sc, prm.s2, prm.log_beta, prm.beta_sigma, list(prm.ddif)[:prm.n_ddif],
+                                         prm.superdye_rate, prm.superdye_factor, prm.seed, prm.first_molecule, int(num_simulations))
     else:
-        out = {k: v.cpu().numpy() for k, v in simulate_device_prm(prm, num_simulations, device).items()}
+        out = _engine.to_host(simulate_device_prm(prm, num_simulations, device))
         out["edman_fail"], out["category"] = out["edman_fail"].view(np.uint64), out["category"].view(np.uint64)
     out.update(meta)
     return out
@@ -319,11 +303,6 @@ def convert_to_oldstyle(merged_dye_count_results):
 
 # ---- the chain on the device ----
 
-def _decrements_of_row(counts):
-    dec = tuple(('A', c) for c in range(1, len(counts)) for _ in range(counts[c - 1] - counts[c]))
-    return dec if dec else (('A', 0),)
-
-
 def signals_from_device(sim, fit=None):
     """(molecular_error_signals, signals, total_count, none_count) of a simulation on the device and, if given, the fit of
     its kept molecules: torch.unique over the count rows and over the winning rows; only the unique rows reach Python."""
@@ -331,10 +310,8 @@ def signals_from_device(sim, fit=None):
     from . import lognormal as LN
     keep = sim["category"] != 0
     rows, n = torch.unique(sim["counts"][keep], dim=0, return_counts=True)
-    mes = {}
-    for row, k in zip(rows.cpu().tolist(), n.cpu().tolist()):
-        key = (_decrements_of_row(row), row[-1] == 0, row[0])
-        mes[key] = mes.get(key, 0) + k
+    mes, _ = _tracks.tally_signals(((_tracks.decrements_of_row(row), row[-1] == 0, row[0]) for row in rows.cpu().tolist()),
+                                   n.cpu().tolist())
     if fit is None:
         return mes, None, int(keep.sum()), None
     found = fit["status"] == LN.STATUS_FOUND
@@ -342,11 +319,7 @@ def signals_from_device(sim, fit=None):
     if bool(bad.any()):
         raise NotImplementedError("a simulated track has more surviving sequences than the budget, or an invalid length")
     rows, n = torch.unique(fit["best_seq"][found], dim=0, return_counts=True)
-    signals = {}
-    for row, k in zip(rows.cpu().tolist(), n.cpu().tolist()):
-        signal, is_zero, start = LN._signal(tuple(row))
-        key = (signal, is_zero, start)
-        signals[key] = signals.get(key, 0) + k
+    signals, _ = _tracks.tally_signals((LN.signal_of(tuple(row)) for row in rows.cpu().tolist()), n.cpu().tolist())
     total = int(fit["status"].numel())
     return mes, signals, total, total - int(found.sum())
 
@@ -361,11 +334,9 @@ def simulate_and_fit_records(sequence, labels, num_mocks, num_edmans, num_simula
     device tensors `simulation` and `fit`."""
     torch = _engine._torch()
     from . import lognormal as LN
-    if quench_factors is None or len(quench_factors) != max_possible + 2:
-        raise ValueError("quench_factors required for v8+")
     beta, beta_sigma = experimental_parameters['beta'], experimental_parameters['beta_sigma']
-    means = [math.log(beta) + math.log(i + 1.0) - quench_factors[i] for i in range(max_possible + 2)]
-    fit_prm = LN._params(means, beta_sigma, max_possible, allow_multidrop, max_deviation, LN.DEFAULT_BUDGET if budget is None else budget)
+    means = _tracks.log_fluor_means(beta, quench_factors, max_possible)
+    fit_prm = LN.fit_params(means, beta_sigma, max_possible, allow_multidrop, max_deviation, LN.DEFAULT_BUDGET if budget is None else budget)
     sim = simulate_device(sequence, labels, num_mocks, num_edmans, num_simulations, seed, first_molecule, device,
                           **experimental_parameters)
     if not allow_multidrop and sim["counts"].shape[1] == 1:
@@ -376,8 +347,7 @@ def simulate_and_fit_records(sequence, labels, num_mocks, num_edmans, num_simula
     n = int(d_int.shape[0])
     if n:
         d_len = torch.full((n,), int(d_int.shape[1]), dtype=torch.int32, device=d_int.device)
-        with torch.cuda.device(d_int.device):
-            fit = LN.lognormal_device(d_int, d_cat, d_len, None, None, prm=fit_prm)
+        fit = LN.lognormal_device(d_int, d_cat, d_len, None, None, prm=fit_prm)
         mes, signals, total, none_count = signals_from_device(sim, fit)
     else:
         fit = None

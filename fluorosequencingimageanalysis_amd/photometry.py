@@ -35,9 +35,8 @@ def mexican_hat_photometry_metric(images, spots, brim_size=6, radius=9):
     d_img = _engine.to_device_pixels(imgs, fmt)
     d_sp = torch.from_numpy(np.ascontiguousarray(sp.astype(np.int32))).to(d_img.device)
     d_out = torch.empty(len(sp), dtype=torch.float64, device=d_img.device)
-    rc = (N.lib().fsq_mexican_hat_u32 if fmt == N.PIXELS_U32 else N.lib().fsq_mexican_hat)(d_img.data_ptr(), n_fields, H, W, d_sp.data_ptr(), len(sp), int(brim_size), int(radius),
-                                 d_out.data_ptr(), torch.cuda.current_stream(d_img.device).cuda_stream)
-    N.check(rc, "fsq_mexican_hat")
+    _engine.launch(N.lib().fsq_mexican_hat_u32 if fmt == N.PIXELS_U32 else N.lib().fsq_mexican_hat, "fsq_mexican_hat", d_img.device,
+                   d_img.data_ptr(), n_fields, H, W, d_sp.data_ptr(), len(sp), int(brim_size), int(radius), d_out.data_ptr())
     return d_out.cpu().numpy()
 
 

@@ -22,10 +22,11 @@ import ctypes
 
 import numpy as np
 
-from . import _native as N
+from . import _host_remainder
 from . import _native_remainder as NR
+from . import _tracks
 from . import engine as _engine
-from .lognormal import category_word
+from .lognormal import unwind_photometries
 from .pflib import _py2_round, _py2_str
 
 MAX_FRAMES = NR.MAX_FRAMES
@@ -45,10 +46,6 @@ def _check_frames(F):
         raise ValueError("at least one frame is needed")
     if F > MAX_FRAMES:
         raise NotImplementedError("tracks are limited to %d frames" % MAX_FRAMES)
-
-
-def _all_on(F):
-    return np.uint64((1 << F) - 1)
 
 
 # ---- the device route ----
@@ -83,83 +80,26 @@ def remainder_adjust_device(d_intensity, d_category, d_seg_off, mode='ratio', mi
            "adjustment": torch.empty((S, F), dtype=torch.float64, device=dev),
            "n_remainders": torch.empty(S, dtype=torch.int32, device=dev),
            "kept": torch.empty(S, dtype=torch.uint8, device=dev)}
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.fsq_remainder_adjust(d_intensity.data_ptr(), d_category.data_ptr(), d_seg_off.data_ptr(), n, F, S, ctypes.byref(prm),
-                                    out["adjustment"].data_ptr(), out["n_remainders"].data_ptr(), out["kept"].data_ptr(),
-                                    out["adjusted"].data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_remainder_adjust")
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_remainder_adjust, "fsq_remainder_adjust", dev, d_intensity.data_ptr(), d_category.data_ptr(),
+                   d_seg_off.data_ptr(), n, F, S, ctypes.byref(prm), out["adjustment"].data_ptr(), out["n_remainders"].data_ptr(),
+                   out["kept"].data_ptr(), out["adjusted"].data_ptr(), ws.data_ptr(), ws_bytes)
     return out
-
-
-# ---- the host route ----
-
-def _median(values):
-    """np.median of a 1-D float64 array, NaN for an empty one (numpy warns and gives NaN)."""
-    return np.float64(np.nan) if len(values) == 0 else np.median(values)
-
-
-def _adjust_host(rows, cats, seg_off, mode, minimum):
-    """What fsq_remainder_adjust computes, with numpy: rows float64 [n, F], cats uint64 [n], seg_off int64 [S + 1]."""
-    n, F = rows.shape
-    S = len(seg_off) - 1
-    remainder = (cats & _all_on(F)) == _all_on(F)
-    adjusted, adjustment = np.zeros((n, F)), np.empty((S, F))
-    n_remainders, kept = np.zeros(S, np.int32), np.zeros(S, np.uint8)
-    with np.errstate(all='ignore'):
-        for s in range(S):
-            a, b = int(seg_off[s]), int(seg_off[s + 1])
-            block = rows[a:b]
-            rem = block[remainder[a:b]]
-            R = len(rem)
-            if mode == NR.MODE_RATIO:
-                m = np.median(rem, axis=1)[:, None] if R else np.zeros((0, 1))
-                values = (rem - m) / m
-            else:
-                values = rem
-            med = np.array([_median(values[:, f]) for f in range(F)])
-            adjustment[s] = med if mode == NR.MODE_RATIO else med - med[0]
-            n_remainders[s] = R
-            kept[s] = R >= minimum and (mode == NR.MODE_RATIO or R >= 1)
-            if kept[s]:
-                adjusted[a:b] = block * (1.0 - adjustment[s]) if mode == NR.MODE_RATIO else block - adjustment[s]
-    return {"adjusted": adjusted, "adjustment": adjustment, "n_remainders": n_remainders, "kept": kept}
 
 
 # ---- arrays ----
 
-def _category_words(categories, n, F):
-    if isinstance(categories, np.ndarray) and categories.ndim == 1 and categories.dtype.kind in "iu":
-        cats = np.ascontiguousarray(categories).astype(np.uint64)
-    else:
-        categories = list(categories)
-        if any(len(c) != F for c in categories):
-            raise ValueError("every track needs exactly %d category entries" % F)
-        cats = np.array([category_word(c) for c in categories], dtype=np.uint64)
-    if len(cats) != n:
-        raise ValueError("one category per track")
-    return cats
-
-
 def _checked_rows(intensities, num_frames=None):
     """float64 [n, F] after the checks the module docstring names."""
-    if isinstance(intensities, np.ndarray) and intensities.ndim == 2:
-        rows = intensities
-        F = rows.shape[1] if num_frames is None else int(num_frames)
-    else:
-        seqs = [np.asarray(s).reshape(-1) for s in intensities]
-        F = int(num_frames) if num_frames is not None else (len(seqs[0]) if seqs else 1)
-        if any(len(s) != F for s in seqs):
-            raise ValueError("every track needs exactly %d intensities" % F)
-        rows = np.array(seqs).reshape(len(seqs), F) if seqs else np.zeros((0, F))
-    if rows.shape[1] != F:
-        raise ValueError("every track needs exactly %d intensities" % F)
-    _check_frames(F)
-    if rows.dtype.kind not in "fiub":
+    two_d = isinstance(intensities, np.ndarray) and intensities.ndim == 2
+    seqs = intensities if two_d else [np.asarray(s).reshape(-1) for s in intensities]
+    F = int(num_frames) if num_frames is not None else seqs.shape[1] if two_d else len(seqs[0]) if seqs else 1
+    if any(s.dtype.kind not in "fiub" for s in ([seqs] if two_d else seqs)):
         raise ValueError("finite real intensities are needed")
+    rows, _ = _tracks.pack_rows(seqs, width=F, width_error="every track needs exactly %d intensities" % F)
+    _check_frames(F)
     if rows.shape[0] >= 1 << 31:
         raise ValueError("fewer than 2^31 tracks are needed")
-    rows = np.ascontiguousarray(rows, dtype=np.float64)
     if not np.isfinite(rows).all():
         raise ValueError("intensities must be finite")
     if rows.size and np.abs(rows).max() > MAX_MAGNITUDE:
@@ -177,6 +117,16 @@ def _grouped(ids):
     return order, unique, seg_off
 
 
+def _adjust(rows, cats, seg_off, mode, minimum_r_per_field, device):
+    """remainder_adjust_device's dict as arrays for grouped host arrays: with numpy for device=None, else on that GPU."""
+    if device is None:
+        return _host_remainder.adjust(rows, cats, seg_off, _mode(mode), int(minimum_r_per_field))
+    torch = _engine._torch()
+    dev = torch.device(device)
+    return _engine.to_host(remainder_adjust_device(torch.from_numpy(rows).to(dev), torch.from_numpy(cats.view(np.int64)).to(dev),
+                                                   torch.from_numpy(seg_off).to(dev), mode, minimum_r_per_field))
+
+
 def remainder_adjust_records(intensities, categories, segments, mode='ratio', minimum_r_per_field=5, device="cuda"):
     """The correction of many tracks in one call, as arrays.
 
@@ -185,7 +135,7 @@ def remainder_adjust_records(intensities, categories, segments, mode='ratio', mi
     tracks are grouped stably by ascending id.  device  where it runs; None: with numpy on the host.
     Returns a dict of NumPy arrays: adjusted float64 [n, F] in the caller's order, segment_ids (ascending), and per segment id
     adjustment float64 [S, F], n_remainders int32 [S] and kept uint8 [S]."""
-    m = _mode(mode)
+    _mode(mode)
     if hasattr(intensities, "is_cuda"):                            # a torch tensor
         torch = _engine._torch()
         d_int = intensities.contiguous()
@@ -200,7 +150,7 @@ def remainder_adjust_records(intensities, categories, segments, mode='ratio', mi
             raise ValueError("intensities must be finite")
         if n and float(d_int.abs().max()) > MAX_MAGNITUDE:
             raise ValueError("intensities are limited to a magnitude of 2^52")
-        d_cat = categories if torch.is_tensor(categories) else torch.from_numpy(_category_words(categories, n, F).view(np.int64))
+        d_cat = categories if torch.is_tensor(categories) else torch.from_numpy(_tracks.category_words(categories, n, F).view(np.int64))
         d_cat = d_cat.to(dev).contiguous()
         d_ids = (segments if torch.is_tensor(segments) else torch.from_numpy(np.asarray(segments).astype(np.int64))).to(dev).reshape(-1)
         if int(d_cat.numel()) != n or int(d_ids.numel()) != n:
@@ -212,25 +162,17 @@ def remainder_adjust_records(intensities, categories, segments, mode='ratio', mi
         out = remainder_adjust_device(d_int[d_order].contiguous(), d_cat[d_order].contiguous(), d_off, mode, minimum_r_per_field)
         d_adjusted = torch.empty_like(out["adjusted"])
         d_adjusted[d_order] = out["adjusted"]
-        host = {k: v.cpu().numpy() for k, v in out.items()}
+        host = _engine.to_host(out)
         host["adjusted"], host["segment_ids"] = d_adjusted.cpu().numpy(), d_unique.cpu().numpy()
         return host
     rows = _checked_rows(intensities)
     n, F = rows.shape
-    cats = _category_words(categories, n, F)
+    cats = _tracks.category_words(categories, n, F)
     ids = np.asarray(segments).reshape(-1)
     if len(ids) != n:
         raise ValueError("one segment per track")
     order, unique, seg_off = _grouped(ids)
-    g_rows, g_cats = np.ascontiguousarray(rows[order]), np.ascontiguousarray(cats[order])
-    if device is None:
-        host = _adjust_host(g_rows, g_cats, seg_off, m, int(minimum_r_per_field))
-    else:
-        torch = _engine._torch()
-        dev = torch.device(device)
-        out = remainder_adjust_device(torch.from_numpy(g_rows).to(dev), torch.from_numpy(g_cats.view(np.int64)).to(dev),
-                                      torch.from_numpy(seg_off).to(dev), mode, minimum_r_per_field)
-        host = {k: v.cpu().numpy() for k, v in out.items()}
+    host = _adjust(np.ascontiguousarray(rows[order]), np.ascontiguousarray(cats[order]), seg_off, mode, minimum_r_per_field, device)
     adjusted = np.empty_like(host["adjusted"])
     adjusted[order] = host["adjusted"]
     host["adjusted"], host["segment_ids"] = adjusted, unique
@@ -260,16 +202,9 @@ def _adjust_dict(photometries, num_frames, minimum_r_per_field, mode, device):
     keys, seg, tracks = _unwound(photometries, num_frames)
     F = int(num_frames)
     rows = _checked_rows([t[2] for t in tracks], F)
-    cats = np.array([category_word(t[1]) for t in tracks], dtype=np.uint64)
+    cats = _tracks.category_words([t[1] for t in tracks], len(tracks))
     seg_off = np.searchsorted(np.asarray(seg, dtype=np.int64), np.arange(len(keys) + 1)).astype(np.int64)
-    if device is None:
-        host = _adjust_host(rows, cats, seg_off, _mode(mode), int(minimum_r_per_field))
-    else:
-        torch = _engine._torch()
-        dev = torch.device(device)
-        out = remainder_adjust_device(torch.from_numpy(rows).to(dev), torch.from_numpy(cats.view(np.int64)).to(dev),
-                                      torch.from_numpy(seg_off).to(dev), mode, minimum_r_per_field)
-        host = {k: v.cpu().numpy() for k, v in out.items()}
+    host = _adjust(rows, cats, seg_off, mode, minimum_r_per_field, device)
     adjusted, medians = {}, {}
     for s, (channel, field) in enumerate(keys):
         if not host["kept"][s]:
@@ -297,13 +232,10 @@ def adjusted_photometries_as_read(adjusted):
     """The nested dict lognormal.read_track_photometries_csv(path, downstep_filtered=False)[0] gives on the file
     write_adjusted_csv writes from `adjusted`, without the file: every value through Python 2's str() and the reader's
     int(round(float(text))), rows numbered as written.  (A value that is not finite raises as the reader does.)"""
-    d, r = {}, 0
-    for channel, cdict in adjusted.items():
-        for field, fdict in cdict.items():
-            for (h, w), (category, intensities, _) in fdict.items():
-                r += 1                                              # (the header is row 0)
-                vals = tuple(int(_py2_round(float(_py2_str(np.float64(v))))) for v in intensities)
-                d.setdefault(str(channel), {}).setdefault(int(field), {}).setdefault((int(h), int(w)), (tuple(bool(c) for c in category), vals, r))
+    d = {}
+    for r, (channel, field, h, w, category, intensities, _) in enumerate(unwind_photometries(adjusted), 1):   # (the header is row 0)
+        vals = tuple(int(_py2_round(float(_py2_str(np.float64(v))))) for v in intensities)
+        d.setdefault(str(channel), {}).setdefault(int(field), {}).setdefault((int(h), int(w)), (tuple(bool(c) for c in category), vals, r))
     return d
 
 
@@ -314,8 +246,6 @@ def write_adjusted_csv(adjusted, num_frames, path):
     with open(path, 'w', newline='') as f:
         w = csv.writer(f)
         w.writerow(["CHANNEL", "FIELD", "H", "W", "CATEGORY"] + ["FRAME " + str(frame) for frame in range(num_frames)])
-        for channel, cdict in adjusted.items():
-            for field, fdict in cdict.items():
-                for (h, ww), (category, intensities, _) in fdict.items():
-                    w.writerow([str(channel), str(field), str(h), str(ww), str(category)] + [_py2_str(np.float64(v)) for v in intensities])
+        for channel, field, h, ww, category, intensities, _ in unwind_photometries(adjusted):
+            w.writerow([str(channel), str(field), str(h), str(ww), str(category)] + [_py2_str(np.float64(v)) for v in intensities])
     return path

@@ -11,6 +11,7 @@ import numpy as np
 from . import _native as N
 from . import _native_sequence as NQ
 from . import engine as _engine
+from ._tracks import pattern_to_tuple                             # noqa: F401  (its old place)
 
 METHODS = {"mexican_hat": NQ.METHOD_MEXICAN_HAT, "simple": NQ.METHOD_SIMPLE}
 FIRST_OFFSET_ERROR = "The first image's offset must be (0, 0) by definiton."          # flexlibrary.py:581-583
@@ -81,13 +82,12 @@ def run_device(d_frames, d_trace_hw, d_trace_seq, d_offsets, wide=False, method=
            "flags": torch.empty((m, F), dtype=torch.uint8, device=dev),
            "category": torch.empty(m, dtype=torch.int64, device=dev),
            "trace_valid": torch.empty(m, dtype=torch.uint8, device=dev)}
-    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-    fn = L.fsq_sequence_photometry_u32 if wide else L.fsq_sequence_photometry
-    rc = fn(d_frames.data_ptr(), n_seq, F, H, W, d_trace_hw.data_ptr(), d_trace_seq.data_ptr(), n, d_offsets.data_ptr(),
-            int(radius), int(brim_size), int(spot_size), int(method), 1 if interpolate else 0, out["hw"].data_ptr(),
-            out["photometry"].data_ptr(), out["flags"].data_ptr(), out["category"].data_ptr(), out["trace_valid"].data_ptr(),
-            ws.data_ptr(), int(ws_bytes), torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_sequence_photometry")
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_sequence_photometry_u32 if wide else L.fsq_sequence_photometry, "fsq_sequence_photometry", dev,
+                   d_frames.data_ptr(), n_seq, F, H, W, d_trace_hw.data_ptr(), d_trace_seq.data_ptr(), n, d_offsets.data_ptr(),
+                   int(radius), int(brim_size), int(spot_size), int(method), 1 if interpolate else 0, out["hw"].data_ptr(),
+                   out["photometry"].data_ptr(), out["flags"].data_ptr(), out["category"].data_ptr(), out["trace_valid"].data_ptr(),
+                   ws.data_ptr(), int(ws_bytes))
     for k in out:
         out[k] = out[k][:n]
     out["_ws"] = ws                   # (kept alive until the caller has read the outputs)
@@ -111,12 +111,10 @@ def category_counts_device(d_category, d_trace_seq, d_select=None):
     g_cnt = torch.empty(m, dtype=torch.int32, device=dev)
     g_first = torch.empty(m, dtype=torch.int32, device=dev)
     g_n = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
-    rc = L.fsq_sequence_category_counts(d_category.data_ptr(), d_trace_seq.data_ptr(),
-                                        d_select.data_ptr() if d_select is not None else None, n, g_seq.data_ptr(),
-                                        g_pat.data_ptr(), g_cnt.data_ptr(), g_first.data_ptr(), g_n.data_ptr(), ws.data_ptr(),
-                                        int(ws_bytes), torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_sequence_category_counts")
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_sequence_category_counts, "fsq_sequence_category_counts", dev, d_category.data_ptr(), d_trace_seq.data_ptr(),
+                   d_select.data_ptr() if d_select is not None else None, n, g_seq.data_ptr(), g_pat.data_ptr(), g_cnt.data_ptr(),
+                   g_first.data_ptr(), g_n.data_ptr(), ws.data_ptr(), int(ws_bytes))
     return g_seq, g_pat, g_cnt, g_first, g_n, ws
 
 
@@ -181,9 +179,3 @@ def sequence_photometry_records(frames, trace_hw, trace_seq, offsets, method='me
     if counts:
         out["counts"] = _counts_to_host(*res[:5])
     return out
-
-
-def pattern_to_tuple(pattern, n_frames):
-    """uint64 pattern -> the reference's tuple of booleans (Experiment.trace_to_binary)."""
-    p = int(pattern)
-    return tuple(bool((p >> f) & 1) for f in range(n_frames))

@@ -16,7 +16,7 @@ from datetime import datetime
 from math import log
 from time import time
 
-from . import peptide_simulator
+from . import _host_lognormal, _tracks, peptide_simulator
 from .pflib import _epoch_to_hash
 
 MAX_POSSIBLE = 5                    # (simulate_peptide.py:197)
@@ -70,33 +70,19 @@ def photometries_of_records(records):
 
 
 def molecular_error_signals_of_records(records, kept):
-    out = {}
     counts = records["counts"].tolist()
-    for i in kept:
-        key = (peptide_simulator._decrements_of_row(counts[i]), counts[i][-1] == 0, counts[i][0])
-        out[key] = out.get(key, 0) + 1
-    return out
+    return _tracks.tally_signals((_tracks.decrements_of_row(counts[i]), counts[i][-1] == 0, counts[i][0]) for i in kept)[0]
 
 
 def host_fit(photometries, beta, beta_sigma, max_possible, allow_multidrop, max_deviation, quench_factors):
     """(signals, total_count, none_count) of lognormal.photometries_lognormal_fit with the Python restatement of the fit
-    (tests/_lognormal_reference.py of the source tree)."""
-    import importlib.util
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "_lognormal_reference.py")
-    spec = importlib.util.spec_from_file_location("_lognormal_reference", path)
-    R = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(R)
-    means = [log(beta) + log(i + 1.0) - quench_factors[i] for i in range(max_possible + 2)]
-    signals, none_count, total = {}, 0, 0
-    for category, intensities, _ in photometries['ch1'][0].values():
-        signal, is_zero, _, _, _, _, start = R.intensities_to_signal(list(intensities), beta_sigma, max_possible, allow_multidrop,
-                                                                      max_deviation, category, means)
-        total += 1
-        if signal is None:
-            none_count += 1
-        else:
-            signals[(signal, is_zero, start)] = signals.get((signal, is_zero, start), 0) + 1
-    return signals, total, none_count
+    (_host_lognormal.py)."""
+    means = _tracks.log_fluor_means(beta, quench_factors, max_possible)
+    tracks = photometries['ch1'][0].values()
+    fits = [_host_lognormal.intensities_to_signal(list(intensities), beta_sigma, max_possible, allow_multidrop, max_deviation,
+                                                  category, means) for category, intensities, _ in tracks]
+    signals, none_count = _tracks.tally_signals((f[0], f[1], f[6]) for f in fits)
+    return signals, len(fits), none_count
 
 
 def main(argv=None):

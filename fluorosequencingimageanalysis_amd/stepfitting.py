@@ -16,9 +16,9 @@ import math
 
 import numpy as np
 
-from . import _native as N
 from . import _native_chisq as NC
 from . import _native_stepfit as NS
+from . import _tracks
 from . import engine as _engine
 
 CK_WINDOW_LENGTHS = (2, 4, 8, 16)     # the live path's CK windows (flexlibrary.py:1436)
@@ -150,35 +150,12 @@ def plateau_starts(plateaus):
     return set(start for start, _stop, _height in plateaus)
 
 
-def _rows(sequences, none_is_zero, min_frames, nan_error):
-    """Sequences (a 2-D array or a list of ragged ones) -> (float64 [n, max_frames] host rows, int32 lengths).  nan_error: the
-    ValueError text (% the trace's index) for a sequence that holds a NaN, or None to let NaN pass."""
-    conv = (lambda v: 0.0 if v is None else float(v)) if none_is_zero else float
-    if isinstance(sequences, np.ndarray) and sequences.ndim == 2:
-        seqs = [np.asarray(r, dtype=np.float64) for r in sequences]
-    else:
-        seqs = [np.array([conv(v) for v in s], dtype=np.float64) for s in sequences]
-    lens = np.array([len(s) for s in seqs], dtype=np.int32)
-    if len(seqs) and lens.min() < min_frames:
-        raise ValueError("every photometry trace needs at least one frame")
-    rows = np.zeros((len(seqs), max(int(lens.max()) if len(seqs) else 1, 1)), dtype=np.float64)
-    for i, s in enumerate(seqs):
-        if nan_error is not None and np.isnan(s).any():
-            raise ValueError(nan_error % i)
-        rows[i, :len(s)] = s
-    return rows, lens
-
-
 def _as_rows(photometries, photometry_min):
     """Photometry sequences -> (float64 [n, max_frames] host rows, int32 lengths).  None frames count 0."""
     # (the reference's plateau comparisons depend on object identity with NaN heights: no pinnable result)
-    return _rows(photometries, True, 1,
-                 "trace %d holds a NaN photometry; pass photometry_min to clamp it" if photometry_min is None else None)
-
-
-def _lum_rows(sequences):
-    """Luminosity sequences -> (float64 [n, max_frames] host rows, int32 lengths); a NaN has no pinnable reference result."""
-    return _rows(sequences, False, 0, "trace %d holds a NaN luminosity")
+    return _tracks.pack_rows(photometries, none_is_zero=True, min_frames=1,
+                             short_error="every photometry trace needs at least one frame",
+                             nan_error="trace %d holds a NaN photometry; pass photometry_min to clamp it" if photometry_min is None else None)
 
 
 def _params(mirror_start, chung_kennedy, p_threshold, photometry_min, window_radius=LIVE_WINDOW_RADIUS, drop_sort=True,
@@ -246,18 +223,24 @@ def run_device(d_phot, d_len, max_frames, prm, want_p=False, pair_cap=0):
     if pair_cap > 0:
         out["pair_p"] = torch.empty((n, pair_cap), dtype=torch.float64, device=dev)
         out["pair_n"] = torch.empty(n, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+    ws = _engine.workspace(dev, ws_bytes)
     o = out
-    rc = L.fsq_stepfit_traces(d_phot.data_ptr(), d_len.data_ptr(), n, int(max_frames), ctypes.byref(prm), o["ck"].data_ptr(),
-                              o["pl_start"].data_ptr(), o["pl_stop"].data_ptr(), o["pl_h"].data_ptr(), o["pl_n"].data_ptr(),
-                              o["tf_start"].data_ptr(), o["tf_stop"].data_ptr(), o["tf_h"].data_ptr(), o["tf_n"].data_ptr(),
-                              o["status"].data_ptr(), o["p"].data_ptr() if want_p else None,
-                              o["pair_p"].data_ptr() if pair_cap > 0 else None, o["pair_n"].data_ptr() if pair_cap > 0 else None,
-                              int(pair_cap), ws.data_ptr(), int(ws_bytes),
-                              torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_stepfit_traces")
+    _engine.launch(L.fsq_stepfit_traces, "fsq_stepfit_traces", dev, d_phot.data_ptr(), d_len.data_ptr(), n, int(max_frames),
+                   ctypes.byref(prm), o["ck"].data_ptr(), o["pl_start"].data_ptr(), o["pl_stop"].data_ptr(), o["pl_h"].data_ptr(),
+                   o["pl_n"].data_ptr(), o["tf_start"].data_ptr(), o["tf_stop"].data_ptr(), o["tf_h"].data_ptr(), o["tf_n"].data_ptr(),
+                   o["status"].data_ptr(), o["p"].data_ptr() if want_p else None, o["pair_p"].data_ptr() if pair_cap > 0 else None,
+                   o["pair_n"].data_ptr() if pair_cap > 0 else None, int(pair_cap), ws.data_ptr(), int(ws_bytes))
     out["_ws"] = ws                   # (kept alive until the caller has read the outputs)
     return out
+
+
+def raise_for_fit_status(st):
+    """run_device's status words as the exception of the first trace that has one."""
+    if (st == NS.STATUS_UNSUPPORTED).any():
+        raise NotImplementedError("trace %d: a t-filter pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
+                                  "is not restated)" % int(np.flatnonzero(st == NS.STATUS_UNSUPPORTED)[0]))
+    if (st != NS.STATUS_OK).any():
+        raise ValueError("trace %d: invalid length" % int(np.flatnonzero(st != NS.STATUS_OK)[0]))
 
 
 def _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min, want_p=False, device=None, **kw):
@@ -268,16 +251,8 @@ def _run(photometries, mirror_start, chung_kennedy, p_threshold, photometry_min,
         return None, lens, prm
     torch = _engine._torch()
     dev = torch.device(device or "cuda")
-    d_phot = torch.from_numpy(rows).to(dev)
-    d_len = torch.from_numpy(lens).to(dev)
-    out = run_device(d_phot, d_len, rows.shape[1], prm, want_p=want_p)
-    host = {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
-    st = host["status"]
-    if (st == NS.STATUS_UNSUPPORTED).any():
-        raise NotImplementedError("trace %d: a t-filter pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
-                                  "is not restated)" % int(np.flatnonzero(st == NS.STATUS_UNSUPPORTED)[0]))
-    if (st != NS.STATUS_OK).any():
-        raise ValueError("trace %d: invalid length" % int(np.flatnonzero(st != NS.STATUS_OK)[0]))
+    host = _engine.to_host(run_device(torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev), rows.shape[1], prm, want_p=want_p))
+    raise_for_fit_status(host["status"])
     host["rows"], host["lens"] = rows, lens
     return host, lens, prm
 
@@ -372,13 +347,11 @@ def t_test_filter(luminosities, plateaus, p_threshold, drop_sort=True, no_merge_
     ws_bytes = L.fsq_stepfit_ttest_filter_workspace_bytes(1, n)
     out = _plateau_out(1, n, dev, False)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
-    rc = L.fsq_stepfit_ttest_filter(d["lum"].data_ptr(), d["len"].data_ptr(), 1, n, d["s"].data_ptr(), d["o"].data_ptr(),
-                                    d["h"].data_ptr(), d["n"].data_ptr(), float(p_threshold), 1 if drop_sort else 0,
-                                    int(no_merge_start), out["start"].data_ptr(), out["stop"].data_ptr(), out["height"].data_ptr(),
-                                    out["count"].data_ptr(), status.data_ptr(), None, None, 0, ws.data_ptr(), int(ws_bytes),
-                                    torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_stepfit_ttest_filter")
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_stepfit_ttest_filter, "fsq_stepfit_ttest_filter", dev, d["lum"].data_ptr(), d["len"].data_ptr(), 1, n,
+                   d["s"].data_ptr(), d["o"].data_ptr(), d["h"].data_ptr(), d["n"].data_ptr(), float(p_threshold), 1 if drop_sort else 0,
+                   int(no_merge_start), out["start"].data_ptr(), out["stop"].data_ptr(), out["height"].data_ptr(),
+                   out["count"].data_ptr(), status.data_ptr(), None, None, 0, ws.data_ptr(), int(ws_bytes))
     st = int(status.cpu()[0])
     if st == NS.STATUS_UNSUPPORTED:
         raise NotImplementedError("t_test_filter: a pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
@@ -459,13 +432,11 @@ def chisq_device(d_lum, d_len, num_steps_multiplier=1, num_steps=None, min_step_
         for k in ("best_res", "counter_res", "S"):
             out[k] = torch.zeros((n, fit_cap), dtype=torch.float64, device=dev)
         out["counter_n"] = torch.zeros((n, fit_cap), dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+    ws = _engine.workspace(dev, ws_bytes)
     opt = [out[k].data_ptr() for k in ("best_res", "counter_res", "counter_n", "S")] if fit_cap > 0 else [None] * 4
-    rc = L.fsq_chisq_step_fit(d_lum.data_ptr(), d_len.data_ptr(), n, max_frames, ctypes.byref(prm), out["start"].data_ptr(),
-                              out["stop"].data_ptr(), out["height"].data_ptr(), out["count"].data_ptr(),
-                              out["n_fits"].data_ptr(), opt[0], opt[1], opt[2], opt[3], int(fit_cap), out["status"].data_ptr(),
-                              ws.data_ptr(), int(ws_bytes), torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_chisq_step_fit")
+    _engine.launch(L.fsq_chisq_step_fit, "fsq_chisq_step_fit", dev, d_lum.data_ptr(), d_len.data_ptr(), n, max_frames,
+                   ctypes.byref(prm), out["start"].data_ptr(), out["stop"].data_ptr(), out["height"].data_ptr(), out["count"].data_ptr(),
+                   out["n_fits"].data_ptr(), *opt, int(fit_cap), out["status"].data_ptr(), ws.data_ptr(), int(ws_bytes))
     out["_ws"] = ws                   # (kept alive until the caller has read the outputs)
     return out
 
@@ -477,7 +448,7 @@ def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step
     Returns a dict: "trace", "start", "stop", "height" (one entry per plateau, in trace order), "counts" and "n_fits" per
     trace, "lengths" and, when fit_cap > 0, "best_res", "counter_res", "S", "counter_n" ([n, fit_cap], row t valid up to
     n_fits[t]).  Raises the reference's errors for the first trace that has one."""
-    rows, lens = _lum_rows(photometries)
+    rows, lens = _tracks.pack_rows(photometries, none_is_zero=False, nan_error="trace %d holds a NaN luminosity")   # (no pinnable result)
     _chisq_params(num_steps_multiplier, num_steps, min_step_length, min_step_magnitude, ignore_counterfits)
     if len(lens) and lens.max() > NC.MAX_FRAMES:
         raise ValueError("chi_squared_step_fitter: traces are limited to %d frames" % NC.MAX_FRAMES)
@@ -490,9 +461,8 @@ def chisq_records(photometries, num_steps_multiplier=1, num_steps=None, min_step
         return dict(_flat_empty(), n_fits=np.zeros(0, np.int32), lengths=lens)
     torch = _engine._torch()
     dev = torch.device(device or "cuda")
-    out = chisq_device(torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev), num_steps_multiplier, num_steps,
-                       min_step_length, min_step_magnitude, ignore_counterfits, fit_cap)
-    host = {k: v.cpu().numpy() for k, v in out.items() if not k.startswith("_")}
+    host = _engine.to_host(chisq_device(torch.from_numpy(rows).to(dev), torch.from_numpy(lens).to(dev), num_steps_multiplier, num_steps,
+                                        min_step_length, min_step_magnitude, ignore_counterfits, fit_cap))
     st = host["status"]
     if (st == NS.STATUS_UNSUPPORTED).any():
         i = int(np.flatnonzero(st == NS.STATUS_UNSUPPORTED)[0])
@@ -552,14 +522,11 @@ def merge_filter_device(d_lum, d_len, d_start, d_stop, d_h, d_n, mode, min_magni
     n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
     out = _plateau_out(n, mf, dev, True)
     out["status"] = torch.zeros(n, dtype=torch.int32, device=dev)
-    rc = NC.lib().fsq_stepfit_merge_filter(d_lum.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
-                                           d_h.data_ptr(), d_n.data_ptr(), int(mode), 0 if min_magnitude is None else 1,
-                                           0.0 if min_magnitude is None else float(min_magnitude),
-                                           0 if min_noise_ratio is None else 1,
-                                           0.0 if min_noise_ratio is None else float(min_noise_ratio), out["start"].data_ptr(),
-                                           out["stop"].data_ptr(), out["height"].data_ptr(), out["count"].data_ptr(),
-                                           out["status"].data_ptr(), None, 0, torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_stepfit_merge_filter")
+    _engine.launch(NC.lib().fsq_stepfit_merge_filter, "fsq_stepfit_merge_filter", dev, d_lum.data_ptr(), d_len.data_ptr(), n, mf,
+                   d_start.data_ptr(), d_stop.data_ptr(), d_h.data_ptr(), d_n.data_ptr(), int(mode), 0 if min_magnitude is None else 1,
+                   0.0 if min_magnitude is None else float(min_magnitude), 0 if min_noise_ratio is None else 1,
+                   0.0 if min_noise_ratio is None else float(min_noise_ratio), out["start"].data_ptr(), out["stop"].data_ptr(),
+                   out["height"].data_ptr(), out["count"].data_ptr(), out["status"].data_ptr(), None, 0)
     return out
 
 
@@ -569,10 +536,9 @@ def r_squared_device(d_lum, d_len, d_start, d_stop, d_h, d_n):
     dev = d_lum.device
     n, mf = int(d_lum.shape[0]), int(d_lum.shape[1])
     out = {"r2": torch.zeros(n, dtype=torch.float64, device=dev), "status": torch.zeros(n, dtype=torch.int32, device=dev)}
-    rc = NC.lib().fsq_stepfit_r_squared(d_lum.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
-                                        d_h.data_ptr(), d_n.data_ptr(), out["r2"].data_ptr(), out["status"].data_ptr(), None, 0,
-                                        torch.cuda.current_stream(dev).cuda_stream)
-    N.check(rc, "fsq_stepfit_r_squared")
+    _engine.launch(NC.lib().fsq_stepfit_r_squared, "fsq_stepfit_r_squared", dev, d_lum.data_ptr(), d_len.data_ptr(), n, mf,
+                   d_start.data_ptr(), d_stop.data_ptr(), d_h.data_ptr(), d_n.data_ptr(), out["r2"].data_ptr(), out["status"].data_ptr(),
+                   None, 0)
     return out
 
 

@@ -14,6 +14,7 @@ import numpy as np
 from . import _native as N
 from . import _native_stepfit as NS
 from . import _native_timetrace as NT
+from . import _tracks
 from . import engine as _engine
 from . import stepfitting as _sf
 from .pflib import _py2_str
@@ -22,10 +23,6 @@ HEADER = ['Trace #', 'Hcoord', 'Wcoord', 'Frame #', 'Photometry']
 STEP_FIT_HEADER = ['Step #', 'Plateau Height', 'Step Size', 'Plateau Length', 'Overall Fit R^2']
 INTERMEDIATES = ('ck_filtered_photometries', 'photometries', 'plateaus', 't_filtered_plateaus')     # (sorted() order)
 TABLE_KEYS = ("plateau_index", "plateau_height", "plateau_length", "step_num", "step_size", "rss", "tss", "r2", "status")
-
-
-def _stream(torch, dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def table_out(n, max_frames, dev):
@@ -43,14 +40,11 @@ def table_device(d_phot, d_len, d_start, d_stop, d_h, d_n, out=None):
     """fsq_timetrace_table on device tensors (float64 / int32 rows of [n, max_frames], int32 [n]); returns a dict of device
     tensors under TABLE_KEYS (`out`, when given, is written in place).  Enqueued on the current stream, not synchronised.
     A trace the device refuses comes back with status 2 and its rows as they were (zeros)."""
-    torch = _engine._torch()
     dev = d_phot.device
     n, mf = int(d_phot.shape[0]), int(d_phot.shape[1])
     out = table_out(n, mf, dev) if out is None else out
-    rc = NT.lib().fsq_timetrace_table(d_phot.data_ptr(), d_len.data_ptr(), n, mf, d_start.data_ptr(), d_stop.data_ptr(),
-                                      d_h.data_ptr(), d_n.data_ptr(), *([out[k].data_ptr() for k in TABLE_KEYS] +
-                                                                        [_stream(torch, dev)]))
-    N.check(rc, "fsq_timetrace_table")
+    _engine.launch(NT.lib().fsq_timetrace_table, "fsq_timetrace_table", dev, d_phot.data_ptr(), d_len.data_ptr(), n, mf,
+                   d_start.data_ptr(), d_stop.data_ptr(), d_h.data_ptr(), d_n.data_ptr(), *[out[k].data_ptr() for k in TABLE_KEYS])
     return out
 
 
@@ -62,10 +56,9 @@ def plateau_values_device(d_start, d_stop, d_h, d_n, want_index=False):
     n, mf = int(d_start.shape[0]), int(d_start.shape[1])
     out = {"height": torch.zeros((n, mf), dtype=torch.float64, device=dev), "status": torch.zeros(n, dtype=torch.int32, device=dev),
            "index": torch.zeros((n, mf), dtype=torch.int32, device=dev) if want_index else None}
-    rc = NT.lib().fsq_plateau_values(d_start.data_ptr(), d_stop.data_ptr(), d_h.data_ptr(), d_n.data_ptr(), n, mf,
-                                     out["height"].data_ptr(), out["index"].data_ptr() if want_index else None,
-                                     out["status"].data_ptr(), _stream(torch, dev))
-    N.check(rc, "fsq_plateau_values")
+    _engine.launch(NT.lib().fsq_plateau_values, "fsq_plateau_values", dev, d_start.data_ptr(), d_stop.data_ptr(), d_h.data_ptr(),
+                   d_n.data_ptr(), n, mf, out["height"].data_ptr(), out["index"].data_ptr() if want_index else None,
+                   out["status"].data_ptr())
     return out
 
 
@@ -100,7 +93,7 @@ def timetrace_table(photometries, plateaus, device=None):
     """The table of many traces: photometries is a 2-D array or a list of ragged sequences (None counts 0), plateaus one list
     of (start, stop, height) per trace.  Returns a dict of numpy arrays under TABLE_KEYS (rows [n, max_frames], row t valid
     for its own length) and "lengths"; raises what save_experiment_as_csv raises for the first trace it would fail on."""
-    rows, lens = _sf._rows(photometries, True, 0, None)
+    rows, lens = _tracks.pack_rows(photometries, none_is_zero=True)
     if len(plateaus) != len(lens):
         raise ValueError("plateaus must hold one list per trace")
     if len(lens) == 0:
@@ -111,8 +104,7 @@ def timetrace_table(photometries, plateaus, device=None):
     st, so, hh, cnt = plateau_rows(plateaus, mf)
     torch = _engine._torch()
     dev = torch.device(device or "cuda")
-    out = table_device(*(torch.from_numpy(a).to(dev) for a in (rows, lens, st, so, hh, cnt)))
-    host = {k: v.cpu().numpy() for k, v in out.items()}
+    host = _engine.to_host(table_device(*(torch.from_numpy(a).to(dev) for a in (rows, lens, st, so, hh, cnt))))
     raise_for_status(host["status"], lens, so, cnt)
     host["lengths"] = lens
     return host
@@ -150,29 +142,26 @@ def timetrace_records(frames, init_hw, search_radius=3, s_n_cutoff=3.0, photomet
                 "photometry": np.zeros((0, F)), "params": params}
     L, LT = N.lib(), NT.lib()
     u32 = fmt == N.PIXELS_U32
-    s = _stream(torch, dev)
     d_fr = _engine.to_device_pixels(fr, fmt, dev)
     d_hw0 = torch.from_numpy(hw0).to(dev)
     d_field = torch.zeros(T, dtype=torch.int32, device=dev)
     d_hw = torch.empty((T, F, 2), dtype=torch.int32, device=dev)
     d_pres = torch.empty((T, F), dtype=torch.uint8, device=dev)
     d_err = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = (L.fsq_centroid_tracking_u32 if u32 else L.fsq_centroid_tracking)(
-        d_fr.data_ptr(), 1, F, H, W, d_hw0.data_ptr(), d_field.data_ptr(), T, int(search_radius), float(s_n_cutoff), None,
-        d_hw.data_ptr(), d_pres.data_ptr(), d_err.data_ptr(), s)
-    N.check(rc, "fsq_centroid_tracking")
+    _engine.launch(L.fsq_centroid_tracking_u32 if u32 else L.fsq_centroid_tracking, "fsq_centroid_tracking", dev, d_fr.data_ptr(), 1, F,
+                   H, W, d_hw0.data_ptr(), d_field.data_ptr(), T, int(search_radius), float(s_n_cutoff), None, d_hw.data_ptr(),
+                   d_pres.data_ptr(), d_err.data_ptr())
     if int(d_err.item()):                                              # (before the positions are used as pixel addresses)
         raise ValueError("cannot convert float NaN to integer")
     d_fhw = torch.empty((T * F, 3), dtype=torch.int32, device=dev)
-    N.check(LT.fsq_timetrace_spot_rows(d_hw.data_ptr(), d_pres.data_ptr(), T, F, d_fhw.data_ptr(), s), "fsq_timetrace_spot_rows")
+    _engine.launch(LT.fsq_timetrace_spot_rows, "fsq_timetrace_spot_rows", dev, d_hw.data_ptr(), d_pres.data_ptr(), T, F, d_fhw.data_ptr())
     d_val = torch.empty(T * F, dtype=torch.float64, device=dev)
-    rc = (L.fsq_mexican_hat_u32 if u32 else L.fsq_mexican_hat)(d_fr.data_ptr(), F, H, W, d_fhw.data_ptr(), T * F, int(brim_size),
-                                                               int(radius), d_val.data_ptr(), s)
-    N.check(rc, "fsq_mexican_hat")
+    _engine.launch(L.fsq_mexican_hat_u32 if u32 else L.fsq_mexican_hat, "fsq_mexican_hat", dev, d_fr.data_ptr(), F, H, W,
+                   d_fhw.data_ptr(), T * F, int(brim_size), int(radius), d_val.data_ptr())
     d_rows = torch.empty((T, F), dtype=torch.float64, device=dev)
     d_len = torch.empty(T, dtype=torch.int32, device=dev)
-    N.check(LT.fsq_timetrace_photometry_rows(d_val.data_ptr(), d_pres.data_ptr(), T, F, d_rows.data_ptr(), d_len.data_ptr(), s),
-            "fsq_timetrace_photometry_rows")
+    _engine.launch(LT.fsq_timetrace_photometry_rows, "fsq_timetrace_photometry_rows", dev, d_val.data_ptr(), d_pres.data_ptr(), T, F,
+                   d_rows.data_ptr(), d_len.data_ptr())
     fit = _sf.run_device(d_rows, d_len, F, prm)
     tab = table_device(d_rows, d_len, fit["tf_start"], fit["tf_stop"], fit["tf_h"], fit["tf_n"])
     dev_out = {"hw": d_hw, "present": d_pres, "photometry": d_rows, "ck_filtered": fit["ck"]}
@@ -182,13 +171,8 @@ def timetrace_records(frames, init_hw, search_radius=3, s_n_cutoff=3.0, photomet
     if include_intermediates:
         pv = plateau_values_device(fit["pl_start"], fit["pl_stop"], fit["pl_h"], fit["pl_n"])
         dev_out["plateaus_height"], dev_out["plateaus_status"] = pv["height"], pv["status"]
-    host = {k: v.cpu().numpy() for k, v in dev_out.items()}
-    fs = host.pop("fit_status")
-    if (fs == NS.STATUS_UNSUPPORTED).any():
-        raise NotImplementedError("trace %d: a t-filter pass sorts >= 64 plateau pairs with a NaN p (CPython's merge sort order "
-                                  "is not restated)" % int(np.flatnonzero(fs == NS.STATUS_UNSUPPORTED)[0]))
-    if (fs != NS.STATUS_OK).any():
-        raise ValueError("trace %d: invalid length" % int(np.flatnonzero(fs != NS.STATUS_OK)[0]))
+    host = _engine.to_host(dev_out)
+    _sf.raise_for_fit_status(host.pop("fit_status"))
     lens = np.full(T, F, np.int32)
     raise_for_status(host["status"], lens, host["tf_stop"], host["tf_n"])
     if include_intermediates:

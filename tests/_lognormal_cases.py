@@ -76,7 +76,7 @@ def random_batch(seed, n, max_possible=5, beta=10000.0, sigma=0.2, t_lo=1, t_hi=
 
 def restated_records(R, intensities, categories, log_fluor_means, beta_sigma, max_possible=5, allow_multidrop=True,
                      max_deviation=3, budget=1 << 22, lengths=None, device=None):
-    """lognormal.lognormal_records computed by the restatement R (tests/_lognormal_reference.py): the same dict of arrays."""
+    """lognormal.lognormal_records computed by the restatement R (_host_lognormal.py): the same dict of arrays."""
     n = len(intensities)
     F = max([len(x) for x in intensities] + [1])
     out = {"status": np.zeros(n, np.int32), "best_seq": np.zeros((n, F), np.uint8), "best_score": np.full(n, -1.0),

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import _binsearch_reference as B
-import _lognormal_reference as R
+from fluorosequencingimageanalysis_amd import _host_lognormal as R
 from _binsearch_cases import (FIXED_BIN_COUNTS, SEEDED_SIZES, cases, golden, non_vacuity_counts, raw_of, same_files_but_for_the_flag,
                               searches, value_sets)
 from _lognormal_cases import chain_csv_text, check_fit_against_record, restated_records

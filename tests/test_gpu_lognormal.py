@@ -1,12 +1,12 @@
 """Lognormal fluor-count fit on the GPU (include/fsq_lognormal.h): bit for bit against the reference's recorded outputs
-(tests/golden/lognormal_tracks.npz) and, for seeded batches, against the Python restatement (tests/_lognormal_reference.py).
+(tests/golden/lognormal_tracks.npz) and, for seeded batches, against the Python restatement (_host_lognormal.py).
 Nothing is compared with a tolerance."""
 import contextlib
 
 import numpy as np
 import pytest
 
-import _lognormal_reference as R
+from fluorosequencingimageanalysis_amd import _host_lognormal as R
 from _lognormal_cases import (chain_csv_text, check_fit_against_record, golden, means_for, random_batch, restated_records,
                               single_cases)
 from _util import _bits

@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-import _lognormal_reference as R
+from fluorosequencingimageanalysis_amd import _host_lognormal as R
 from _lognormal_cases import (chain_csv_text, check_fit_against_record, golden, recorded_fit_info, restated_records,
                               single_cases)
 from _util import ROOT, _bits

@@ -9,8 +9,8 @@ import re
 import numpy as np
 import pytest
 
-import _lognormal_reference as R
-import _peptide_sim_reference as T
+from fluorosequencingimageanalysis_amd import _host_lognormal as R
+from fluorosequencingimageanalysis_amd import _host_peptide_sim as T
 from _peptide_sim_cases import golden, golden_cases, same_records
 from _util import ROOT, _bits
 

@@ -1,4 +1,4 @@
-// check_log_host.cpp - csrc/lognormal/fsq_glibc_log.h compiled for the host, against this machine's log(): the restatement
+// check_log_host.cpp - csrc/libm/fsq_glibc_log.h compiled for the host, against this machine's log(): the restatement
 // holds only plain IEEE fp64 operations and explicit fmas, so the host build computes what the device computes.
 //
 //   g++ -O2 -mfma -ffp-contract=off -o check_log_host tools/check_log_host.cpp && ./check_log_host [N]
@@ -18,7 +18,7 @@
 static inline unsigned long long fsq_bits(double x) { unsigned long long u; memcpy(&u, &x, 8); return u; }
 static inline double fsq_dbl(unsigned long long u) { double x; memcpy(&x, &u, 8); return x; }
 static inline double fsq_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-#include "../fluorosequencingimageanalysis_amd/csrc/lognormal/fsq_glibc_log.h"
+#include "../fluorosequencingimageanalysis_amd/csrc/libm/fsq_glibc_log.h"
 
 int main(int argc, char** argv)
 {

@@ -225,7 +225,7 @@ def main():
     a = ap.parse_args()
     os.environ["FSQ_REFERENCE"] = a.reference
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
     import refload
     refload.REF = a.reference
     refload.load_reference()
@@ -234,7 +234,7 @@ def main():
     jd = load_functions(refload, "jupyter_development.py", ("_pairwise", "grab_ON_OFFS", "ON_OFF_adjust_photometries"),
                         {"np": np, "tee": itertools.tee, "izip": zip})
     jd["unwind_photometries"] = mc.unwind_photometries
-    import _lognormal_reference as R
+    from fluorosequencingimageanalysis_amd import _host_lognormal as R
     out = {}
 
     # ---- (a) single tracks ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """Writes tests/golden/peptide_sim.npz: the reference's peptide_simulator.py run molecule by molecule under the explicit
-Philox draws of tests/_peptide_sim_reference.py, and what simulate_peptide.py makes of one case (convert_to_oldstyle, the
+Philox draws of _host_peptide_sim.py, and what simulate_peptide.py makes of one case (convert_to_oldstyle, the
 photometries CSV, molecular_error_signals).  Data only: parameters, seeds and recorded results.
 
 The reference is loaded at run time through oracle/refload.py.  Its module-level `random` is replaced by an object whose
@@ -94,10 +94,10 @@ def main():
     a = ap.parse_args()
     os.environ["FSQ_REFERENCE"] = a.reference
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
     import refload
     refload.REF = a.reference
-    import _peptide_sim_reference as T
+    from fluorosequencingimageanalysis_amd import _host_peptide_sim as T
     numpy_identities(T)
     print("numpy: lognormal = exp(mean + sigma * z) and the polar normals hold bit for bit")
 
