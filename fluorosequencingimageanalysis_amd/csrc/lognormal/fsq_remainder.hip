@@ -8,10 +8,8 @@
 //   track's median: every lane ranks its intensity against the others' (ties by lane) with F wave shuffles, so nothing is
 //   indexed at run time and nothing goes to scratch.
 // krm_medians, one 256-thread block per (segment, frame) (:3454, :3414): the exact median of the R values, on their
-//   order-preserving 64-bit keys.  Up to FSQ_REMAINDER_LDS_MAX values sit in LDS and every thread ranks its own against all.
-//   Above, a radix select of eight 8-bit passes over the workspace (a 256-bin LDS histogram of the keys that share the prefix
-//   found so far, then one wavefront scans it) finds the lower middle key and how many keys are at most it; where the upper
-//   middle is another key, a ninth pass takes the least key above.  A NaN among the values gives NaN; R = 0 gives NaN.
+//   order-preserving 64-bit keys: select_median of fsq_select_median.h, in LDS up to FSQ_REMAINDER_LDS_MAX values and a
+//   nine-pass radix select over the workspace above.  A NaN among the values gives NaN; R = 0 gives NaN.
 // krm_finish, one thread per segment: kept (:3450, :3412) and, in ADDITIVE mode, median_f - median_0 (:3416).
 // krm_apply, one thread per value (:3468, :3427): 8 bytes read, 8 written.
 //
@@ -22,54 +20,14 @@
 
 #include "../fsq_common.h"
 #include "../../../include/fsq_remainder.h"
+#include "fsq_select_median.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVE = 64;
+constexpr int THREADS = SELECT_THREADS;
+constexpr int WAVE = SELECT_WAVE;
 constexpr int TRACKS_PER_BLOCK = THREADS / WAVE;
-constexpr int LDS_MAX = FSQ_REMAINDER_LDS_MAX;
 static_assert(FSQ_REMAINDER_MAX_FRAMES <= WAVE, "one lane per frame");
-static_assert(LDS_MAX % THREADS == 0, "whole rounds of the block");
-
-typedef unsigned long long u64;
-
-// the key orders as the double does: negative numbers reversed below the positive ones, -0.0 just below +0.0
-__device__ __forceinline__ u64 key_of(double x)
-{
-    const u64 u = (u64)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double value_of(u64 k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// np.median's mean of its one or two middle values.  np.mean is np.add.reduce over the count, and the reduction is
-// a[0] + (0.0 + a[1] + ...): the sum of the others starts from +0.0.  That only shows on zeros: a median of -0.0 is +0.0.
-__device__ __forceinline__ double middle_mean(double a, double b, bool odd)
-{
-    return odd ? a + 0.0 : (a + (0.0 + b)) / 2.0;
-}
-
-// the segment of track i, or -1: seg_off[s] <= i < seg_off[s + 1] with both inside 0 .. n
-__device__ __forceinline__ long long segment_of(const long long* __restrict__ seg_off, long long S, long long n, long long i,
-                                                long long* off, long long* cap)
-{
-    long long a = 0, b = S + 1;                                    // c = #{j <= S : seg_off[j] <= i}
-    while (a < b) {
-        const long long mid = a + ((b - a) >> 1);
-        if (seg_off[mid] <= i) a = mid + 1; else b = mid;
-    }
-    const long long s = a - 1;
-    if (s < 0 || s >= S) return -1;
-    const long long o = seg_off[s], e = seg_off[s + 1];
-    if (o < 0 || e > n || !(o <= i && i < e)) return -1;
-    *off = o;
-    *cap = e - o;
-    return s;
-}
 
 __global__ void __launch_bounds__(THREADS)
 krm_tracks(const double* __restrict__ intensity, const u64* __restrict__ category, const long long* __restrict__ seg_off,
@@ -108,118 +66,19 @@ krm_tracks(const double* __restrict__ intensity, const u64* __restrict__ categor
 __device__ __forceinline__ int remainders_of(const long long* __restrict__ seg_off, const int* __restrict__ n_remainders,
                                              long long n, long long s, long long* off, long long* cap)
 {
-    const long long o = seg_off[s], e = seg_off[s + 1];
-    *off = 0;
-    *cap = 0;
-    if (o < 0 || e > n || e < o) return 0;
-    *off = o;
-    *cap = e - o;
-    const long long r = n_remainders[s];
-    return (int)(r < e - o ? r : e - o);
+    return clamped_count(seg_off, n, s, n_remainders[s], off, cap);
 }
 
 __global__ void __launch_bounds__(THREADS)
 krm_medians(const double* __restrict__ ws_values, const long long* __restrict__ seg_off, const int* __restrict__ n_remainders,
             long long n, int F, double* __restrict__ median)
 {
-    __shared__ u64 s_key[LDS_MAX];
-    __shared__ int s_hist[256];
-    __shared__ u64 s_pick[2];
-    __shared__ int s_digit, s_below, s_equal;
-    const int tid = threadIdx.x;
+    __shared__ SelectShared sh;
     const long long s = blockIdx.x / F;
     const int f = (int)(blockIdx.x % F);
     long long off, cap;
     const int R = remainders_of(seg_off, n_remainders, n, s, &off, &cap);
-    const double* v = ws_values + (long long)F * off + f * cap;    // the R values of (segment s, frame f)
-    double* out = median + s * F + f;
-    if (R <= 0) {                                                  // (every exit below is uniform over the block)
-        if (tid == 0) *out = __builtin_nan("");
-        return;
-    }
-    const int k1 = (R - 1) / 2, k2 = R / 2;
-    if (R <= LDS_MAX) {
-        int nan = 0;
-        for (int e = tid; e < R; e += THREADS) {
-            const double x = v[e];
-            nan |= x != x;
-            s_key[e] = key_of(x);
-        }
-        if (__syncthreads_or(nan)) {
-            if (tid == 0) *out = __builtin_nan("");
-            return;
-        }
-        for (int e = tid; e < R; e += THREADS) {
-            const u64 k = s_key[e];
-            int rank = 0;                                          // #{j : key_j < key_e, or equal and j < e}
-            for (int j = 0; j < R; j++) {
-                const u64 kj = s_key[j];
-                rank += (kj < k || (kj == k && j < e)) ? 1 : 0;
-            }
-            if (rank == k1) s_pick[0] = k;
-            if (rank == k2) s_pick[1] = k;
-        }
-        __syncthreads();
-        if (tid == 0) *out = middle_mean(value_of(s_pick[0]), value_of(s_pick[1]), R & 1);
-        return;
-    }
-    // ---- radix select of the k1-th key, the most significant byte first ----
-    u64 prefix = 0;
-    int below = 0;                                                 // keys less than every key with this prefix
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        s_hist[tid] = 0;
-        __syncthreads();
-        int nan = 0;
-        for (int e = tid; e < R; e += THREADS) {
-            const double x = v[e];
-            nan |= x != x;
-            const u64 k = key_of(x);
-            if (shift == 56 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(int)((k >> shift) & 255)], 1);
-        }
-        if (__syncthreads_or(shift == 56 ? nan : 0)) {
-            if (tid == 0) *out = __builtin_nan("");
-            return;
-        }
-        if (tid < WAVE) {                                          // lane l owns bins 4l .. 4l + 3
-            int c[4], tot = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) { c[q] = s_hist[4 * tid + q]; tot += c[q]; }
-            int incl = tot;
-#pragma unroll
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const int up = __shfl_up(incl, d, WAVE);
-                if (tid >= d) incl += up;
-            }
-            int before = incl - tot;
-            const int want = k1 - below;                           // 0 <= want < the keys with this prefix
-            if (before <= want && want < incl) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (before <= want && want < before + c[q]) { s_digit = 4 * tid + q; s_below = before; s_equal = c[q]; }
-                    before += c[q];
-                }
-            }
-        }
-        __syncthreads();
-        prefix |= (u64)s_digit << shift;
-        below += s_below;
-        __syncthreads();                                           // (s_digit is read before the next pass writes it)
-    }
-    u64 upper = prefix;                                            // the k2-th key
-    const int at_most = below + s_equal;                           // #{key <= prefix}; s_equal is the last pass's
-    if (k2 >= at_most) {                                           // (uniform: below and s_equal are the block's)
-        if (tid == 0) s_pick[0] = ~0ull;
-        __syncthreads();
-        u64 least = ~0ull;
-        for (int e = tid; e < R; e += THREADS) {
-            const u64 k = key_of(v[e]);
-            if (k > prefix && k < least) least = k;
-        }
-        atomicMin(&s_pick[0], least);
-        __syncthreads();
-        upper = s_pick[0];
-    }
-    if (tid == 0) *out = middle_mean(value_of(prefix), value_of(upper), R & 1);
+    select_median(ws_values + (long long)F * off + f * cap, R, median + s * F + f, sh);   // the R values of (segment s, frame f)
 }
 
 __global__ void __launch_bounds__(THREADS)

@@ -8,6 +8,11 @@ histograms of all photometries for alpha alone, also runs on the device with num
 `bin_search_records`, `histogram_counts`; include/fsq_binsearch.h): `optimal_bin_size`, `optimal_bin_count`, `_get_m0Dm1` and
 `last_drop_method_v2` take it with `device=...` and stay on the host with `device=None`.
 
+The whole chain also runs on a track table that stays on the device (`chain_device`, `chain_records`,
+`track_table_from_photometries`, `track_table_from_records`; include/fsq_lognormal_chain.h): the last-drop lists, the ON/OFF
+medians and the adjustment are kernels, only scalars and histograms cross to the host between the steps, and no Python object
+is made per track.  `chain_records(host=True)` is its NumPy twin (_host_lognormal_chain.py).
+
 Limits of the device fit, each raised on the host before anything is launched: 1 .. 64 frames per track
 (NotImplementedError above 64, ValueError for none), max_possible in 1 .. 15 (NotImplementedError above), beta_sigma finite
 and > 0, max_deviation not NaN, finite intensities and finite log_fluor_means (ValueError); allow_upsteps=True is not built
@@ -25,8 +30,10 @@ from math import log, sqrt
 
 import numpy as np
 
+from . import _host_lognormal_chain as HC
 from . import _native_binsearch as NB
 from . import _native_lognormal as NL
+from . import _native_lognormal_chain as NC
 from . import _tracks
 from . import engine as _engine
 from ._tracks import category_word                                # noqa: F401  (its old place)
@@ -561,3 +568,322 @@ def ON_OFF_adjust_photometries(photometries, ON_OFFS, alpha):
                 for i, intensity in enumerate(intensities)]
         adjusted.setdefault(channel, {}).setdefault(field, {}).setdefault((h, w), (category, tuple(vals), row))
     return adjusted
+
+
+# ---- the whole chain on a track table: the records route of lognormal_fitter_v2 ----
+
+def _bin_search_device(d_values, min_n_bins, max_n_bins):
+    """(the first bin count of least cost over min_n_bins .. max_n_bins, its histogram as an int64 array, lo, hi) of a 1-D
+    float64 CUDA tensor, sorted once for both launches; None where all values are equal (the host's case)."""
+    torch = _engine._torch()
+    d_sorted = _sorted(d_values)
+    dev = d_sorted.device
+    lo, hi = d_sorted[[0, -1]].tolist()
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("values must be finite")
+    if lo == hi:
+        return None
+    n = int(d_sorted.numel())
+    d_counts = torch.arange(int(min_n_bins), int(max_n_bins) + 1, dtype=torch.int32, device=dev)
+    d_cost = torch.empty(int(d_counts.numel()), dtype=torch.float64, device=dev)
+    _engine.launch(NB.lib().fsq_histogram_costs, "fsq_histogram_costs", dev, d_sorted.data_ptr(), n, lo, hi, d_counts.data_ptr(),
+                   int(d_counts.numel()), d_cost.data_ptr())
+    n_bins = int(torch.nonzero(d_cost == d_cost.min())[0]) + int(min_n_bins)
+    d_hist = torch.empty(n_bins, dtype=torch.int64, device=dev)
+    _engine.launch(NB.lib().fsq_histogram_counts, "fsq_histogram_counts", dev, d_sorted.data_ptr(), n, lo, hi, n_bins, d_hist.data_ptr())
+    return n_bins, d_hist.cpu().numpy(), lo, hi
+
+
+def _beta_device(d_values):
+    """last_drop_method_v2's (beta, beta_sigma) of the last-drop values on the device: ValueError for none."""
+    if int(d_values.numel()) == 0:
+        raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of an empty last-drop list)
+    found = _bin_search_device(d_values, 10, 1000)
+    if found is None:
+        return HC.beta_of_values(d_values.cpu().numpy())
+    n_bins, hist, lo, hi = found
+    return HC.beta_of_hist(hist, np.linspace(lo, hi, n_bins + 1))
+
+
+def _check_chain_tensors(d_intensity, d_category, d_seg_off=None):
+    torch = _engine._torch()
+    if d_intensity.dim() != 2 or d_category.dim() != 1 or int(d_category.numel()) != int(d_intensity.shape[0]):
+        raise ValueError("[n, F] intensities and [n] categories are needed")
+    F = int(d_intensity.shape[1])
+    if F < 1:
+        raise ValueError("at least one frame is needed")
+    if F > NC.MAX_FRAMES:
+        raise NotImplementedError("tracks are limited to %d frames" % NC.MAX_FRAMES)
+    if int(d_intensity.shape[0]) >= 1 << 31:
+        raise ValueError("fewer than 2^31 tracks are needed")
+    tensors = [d_intensity, d_category] + ([] if d_seg_off is None else [d_seg_off])
+    if d_intensity.dtype != torch.float64 or d_category.element_size() != 8 or not all(t.is_contiguous() for t in tensors):
+        raise ValueError("contiguous float64 intensities and 64-bit categories are needed")
+    if not d_intensity.is_cuda or any(t.device != d_intensity.device for t in tensors):
+        raise ValueError("tensors on one GPU are needed")
+    if d_seg_off is not None:
+        if d_seg_off.dim() != 1 or d_seg_off.numel() < 1 or d_seg_off.dtype != torch.int64:
+            raise ValueError("[S + 1] int64 offsets are needed")
+        if (int(d_seg_off.numel()) - 1) * max(F - 1, 1) >= 1 << 31:
+            raise ValueError("fewer than 2^31 (segment, frame) pairs are needed")
+
+
+def last_drops_device(d_intensity, d_category, truncate=0):
+    """fsq_chain_last_drops on device tensors (float64 [n, F] intensities, 64-bit [n] category words): (values, track_count),
+    the float64 log(I) of every frame f >= truncate that is ON before an OFF frame with I > 0, in (track, frame) order, and
+    the int64 [n] number of them per track.  Two launches with torch.cumsum between them; the total crosses to the host to size
+    `values`."""
+    torch = _engine._torch()
+    _check_chain_tensors(d_intensity, d_category)
+    truncate = int(truncate)
+    if truncate < 0:
+        raise ValueError("truncate must not be negative")
+    truncate = min(truncate, NC.MAX_FRAMES)
+    n, F = int(d_intensity.shape[0]), int(d_intensity.shape[1])
+    dev = d_intensity.device
+    L = NC.lib()
+    d_count = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.float64, device=dev), d_count
+    _engine.launch(L.fsq_chain_last_drops, "fsq_chain_last_drops", dev, d_intensity.data_ptr(), d_category.data_ptr(), n, F, truncate,
+                   None, d_count.data_ptr(), None, 0, None, 0)
+    d_incl = torch.cumsum(d_count, 0)
+    total = int(d_incl[-1])
+    d_values = torch.empty(total, dtype=torch.float64, device=dev)
+    if total:
+        d_off = (d_incl - d_count).contiguous()
+        _engine.launch(L.fsq_chain_last_drops, "fsq_chain_last_drops", dev, d_intensity.data_ptr(), d_category.data_ptr(), n, F,
+                       truncate, d_off.data_ptr(), None, d_values.data_ptr(), total, None, 0)
+    return d_values, d_count
+
+
+def on_off_medians_device(d_intensity, d_category, d_seg_off, d_status, alpha):
+    """fsq_chain_on_off_medians on device tensors: a dict of on_off_median float64 [S, F - 1] (NaN for a key without entries),
+    on_off_count int32 [S, F - 1] and last_beta_median float64 [1].  d_status: int32 [n], the first fit's status.  Enqueued on
+    the current stream, not synchronised."""
+    torch = _engine._torch()
+    _check_chain_tensors(d_intensity, d_category, d_seg_off)
+    n, F, S = int(d_intensity.shape[0]), int(d_intensity.shape[1]), int(d_seg_off.numel()) - 1
+    dev = d_intensity.device
+    if d_status.dtype != torch.int32 or d_status.dim() != 1 or int(d_status.numel()) != n or not d_status.is_contiguous() or d_status.device != dev:
+        raise ValueError("one contiguous int32 status per track is needed")
+    L = NC.lib()
+    ws_bytes = L.fsq_chain_on_off_medians_workspace_bytes(n, F, S)
+    if ws_bytes < 0:
+        raise ValueError("fsq_chain_on_off_medians_workspace_bytes: invalid shape")
+    out = {"on_off_median": torch.empty((S, F - 1), dtype=torch.float64, device=dev),
+           "on_off_count": torch.empty((S, F - 1), dtype=torch.int32, device=dev),
+           "last_beta_median": torch.empty(1, dtype=torch.float64, device=dev)}
+    ws = _engine.workspace(dev, ws_bytes)
+    _engine.launch(L.fsq_chain_on_off_medians, "fsq_chain_on_off_medians", dev, d_intensity.data_ptr(), d_category.data_ptr(),
+                   d_seg_off.data_ptr(), d_status.data_ptr(), n, F, S, float(alpha), out["on_off_median"].data_ptr(),
+                   out["on_off_count"].data_ptr(), out["last_beta_median"].data_ptr(), ws.data_ptr(), ws_bytes)
+    return out
+
+
+def on_off_adjust_device(d_intensity, d_seg_off, alpha, medians):
+    """fsq_chain_on_off_adjust on device tensors: the adjusted float64 [n, F] of on_off_medians_device's dict."""
+    torch = _engine._torch()
+    n, F, S = int(d_intensity.shape[0]), int(d_intensity.shape[1]), int(d_seg_off.numel()) - 1
+    dev = d_intensity.device
+    d_adjusted = torch.empty((n, F), dtype=torch.float64, device=dev)
+    _engine.launch(NC.lib().fsq_chain_on_off_adjust, "fsq_chain_on_off_adjust", dev, d_intensity.data_ptr(), d_seg_off.data_ptr(), n, F, S,
+                   float(alpha), medians["on_off_median"].data_ptr(), medians["on_off_count"].data_ptr(),
+                   medians["last_beta_median"].data_ptr(), d_adjusted.data_ptr(), None, 0)
+    return d_adjusted
+
+
+def _check_fit_status(fit, what):
+    """NotImplementedError for a track over the budget (one scalar crosses to the host)."""
+    worst = int(fit["status"].max()) if int(fit["status"].numel()) else 0
+    if worst >= STATUS_OVER_BUDGET:
+        HC.check_status(fit["status"].cpu().numpy(), what)
+
+
+def chain_device(d_intensity, d_category, d_seg_off, d_field, beta_sigma, max_possible=5, ddif=0.30, allow_multidrop=True,
+                 truncate=0, beta=None, no_adjustment=False, budget=DEFAULT_BUDGET):
+    """lognormal_fitter_v2.main's computation on a track table on the device: float64 [n, F] intensities, 64-bit [n] category
+    words, int64 [S + 1] offsets of the fields' contiguous tracks (d_field, the field number per track, is accepted and not
+    needed: the segments say it).  Returns a dict: the scalars alpha, n_bins, original_beta, original_beta_sigma, adj_beta and
+    adj_beta_sigma, and the device tensors alpha_adjusted [n, F], adjusted [n, F] (the second fit's input), on_off_median and
+    on_off_count [S, F - 1], last_beta_median [1] and fit0, fit1 (lognormal_device's dicts).  Only scalars and histograms of at
+    most 10 000 bins cross to the host; where all values of a bin search are equal, that search's values do too."""
+    torch = _engine._torch()
+    _check_chain_tensors(d_intensity, d_category, d_seg_off)
+    n, F = int(d_intensity.shape[0]), int(d_intensity.shape[1])
+    HC.check_frames(F, allow_multidrop)
+    dev = d_intensity.device
+    if n == 0:
+        raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of no photometries)
+    if not bool(torch.isfinite(d_intensity).all()):
+        raise ValueError("intensities must be finite")
+    quench = tuple([0.0] + [ddif] * (max_possible + 1))
+    d_len = torch.full((n,), F, dtype=torch.int32, device=dev)
+
+    def fit(d_rows, beta_now, what):
+        prm = fit_params(_tracks.log_fluor_means(beta_now, quench, max_possible), beta_sigma, max_possible, allow_multidrop, 3, budget)
+        out = lognormal_device(d_rows, d_category, d_len, None, None, prm=prm)
+        _check_fit_status(out, what)
+        return out
+
+    found = _bin_search_device(d_intensity.reshape(-1), 10, 10000)
+    if found is None:
+        alpha, n_bins = HC.alpha_of_values(d_intensity.cpu().numpy())
+    else:
+        n_bins, hist, lo, hi = found
+        alpha = HC.alpha_of_hist(hist, n_bins, np.float64(lo), np.float64(hi))
+    original_beta, original_beta_sigma = _beta_device(last_drops_device(d_intensity, d_category, truncate)[0])
+    if beta is not None:
+        original_beta = beta
+    d_alpha_adjusted = d_intensity - float(alpha)
+    if not bool(torch.isfinite(d_alpha_adjusted).all()):
+        raise ValueError("intensities must be finite")
+    fit0 = fit(d_alpha_adjusted, original_beta, "the first fit")
+    medians = on_off_medians_device(d_intensity, d_category, d_seg_off, fit0["status"], alpha)
+    d_adjusted = d_alpha_adjusted if no_adjustment else on_off_adjust_device(d_intensity, d_seg_off, alpha, medians)
+    if not bool(torch.isfinite(d_adjusted).all()):
+        raise ValueError("an adjusted intensity is not finite")
+    adj_beta, adj_beta_sigma = _beta_device(last_drops_device(d_adjusted, d_category, 0)[0])
+    if beta is not None:
+        adj_beta = beta
+    fit1 = fit(d_adjusted, adj_beta, "the second fit")
+    return dict(alpha=alpha, n_bins=n_bins, original_beta=original_beta, original_beta_sigma=original_beta_sigma, adj_beta=adj_beta,
+                adj_beta_sigma=adj_beta_sigma, alpha_adjusted=d_alpha_adjusted, adjusted=d_adjusted, fit0=fit0, fit1=fit1, **medians)
+
+
+def tally_device(fit, d_order=None):
+    """(signals, total_count, none_count) of a fit on the device, the keys in the order of each one's first track
+    (_tracks.tally_signals' insertion order): torch.unique over the winning rows and the first index of every unique row;
+    only the unique rows reach Python.  d_order: the caller's index of every track (default: as they stand)."""
+    torch = _engine._torch()
+    status, best_seq = fit["status"], fit["best_seq"]
+    total = int(status.numel())
+    where = torch.nonzero(status == STATUS_FOUND).reshape(-1)
+    if int(where.numel()) == 0:
+        return {}, total, total
+    rows, inverse, counts = torch.unique(best_seq[where], dim=0, return_inverse=True, return_counts=True)
+    index = where if d_order is None else d_order[where]
+    first = torch.full((int(rows.shape[0]),), total, dtype=torch.int64, device=status.device)
+    first.scatter_reduce_(0, inverse.reshape(-1), index.to(torch.int64), reduce="amin")
+    return HC.tally_rows(rows.cpu().tolist(), first.cpu().tolist(), counts.cpu().tolist(), total)
+
+
+def _grouped_by_first_appearance(fields):
+    """(order, field ids, seg_off, segment per track) of one field per track: a stable grouping, the fields in the order of
+    their first track."""
+    fields = np.asarray(fields).reshape(-1)
+    ids, first, inverse = np.unique(fields, return_index=True, return_inverse=True)
+    by_first = np.argsort(first, kind='stable')
+    rank = np.empty(len(ids), np.int64)
+    rank[by_first] = np.arange(len(ids))
+    segment = rank[inverse.reshape(-1)]
+    order = np.argsort(segment, kind='stable')
+    seg_off = np.zeros(len(ids) + 1, np.int64)
+    np.cumsum(np.bincount(segment, minlength=len(ids)), out=seg_off[1:])
+    return order, ids[by_first], seg_off, segment
+
+
+def chain_records(intensities, categories, fields, beta_sigma, max_possible=5, ddif=0.30, allow_multidrop=True, truncate=0,
+                  beta=None, no_adjustment=False, budget=DEFAULT_BUDGET, device=None, host=False):
+    """The chain for a track table on the host, as arrays: intensities, sequences of one length or a [n, F] array; categories,
+    tuples of F booleans or the uint64 words; fields, one integer per track.  Tracks may come in any order: they are grouped by
+    field, stably, the fields in the order of their first track, and everything per track comes back in the caller's order.
+    Returns chain_device's dict as NumPy arrays (fit0 and fit1 dicts of arrays) with field_ids (one per row of on_off_median
+    and on_off_count), segment (the row of every track's field), signals, total_count and none_count of the second fit.
+    host=True: with numpy on the host (_host_lognormal_chain), no GPU needed."""
+    two_d = isinstance(intensities, np.ndarray) and intensities.ndim == 2
+    seqs = intensities if two_d else [np.asarray(s, dtype=np.float64).reshape(-1) for s in intensities]
+    F = seqs.shape[1] if two_d else len(seqs[0]) if len(seqs) else 1
+    HC.check_frames(F, allow_multidrop)
+    rows, _ = _tracks.pack_rows(seqs, width=F, width_error="every track needs exactly %d intensities" % F)
+    n = len(rows)
+    if not np.isfinite(rows).all():
+        raise ValueError("intensities must be finite")
+    cats = _tracks.category_words(categories, n, F)
+    order, field_ids, seg_off, segment = _grouped_by_first_appearance(fields)
+    if len(segment) != n:
+        raise ValueError("one field per track")
+    if n == 0:
+        raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of no photometries)
+    kw = dict(beta_sigma=beta_sigma, max_possible=max_possible, ddif=ddif, allow_multidrop=allow_multidrop, truncate=truncate,
+              beta=beta, no_adjustment=no_adjustment, budget=budget)
+    g_rows, g_cats = np.ascontiguousarray(rows[order]), np.ascontiguousarray(cats[order])
+    if host:
+        out = HC.chain(g_rows, g_cats, seg_off, **kw)
+        signals = None
+    else:
+        torch = _engine._torch()
+        dev = torch.device(device or "cuda")
+        d_out = chain_device(torch.from_numpy(g_rows).to(dev), torch.from_numpy(g_cats.view(np.int64)).to(dev),
+                             torch.from_numpy(seg_off).to(dev), None, **kw)
+        signals = tally_device(d_out["fit1"], torch.from_numpy(order).to(dev))
+        out = {k: (_engine.to_host(v) if isinstance(v, dict) else v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in d_out.items()}
+        out["last_beta_median"] = float(out["last_beta_median"][0])
+
+    def back(a):
+        b = np.empty_like(a)
+        b[order] = a
+        return b
+    for k in ("alpha_adjusted", "adjusted"):
+        out[k] = back(out[k])
+    for k in ("fit0", "fit1"):
+        out[k] = {name: back(a) for name, a in out[k].items()}
+    if signals is None:
+        signals = HC.tally(out["fit1"]["status"], out["fit1"]["best_seq"])
+    out["signals"], out["total_count"], out["none_count"] = signals
+    out["field_ids"], out["segment"] = field_ids, segment
+    return out
+
+
+def track_table_from_photometries(photometries):
+    """The nested dict of one channel as a track table in unwind_photometries' order: (intensity float64 [n, F], category
+    uint64 [n], field int64 [n], hw int64 [n, 2], row int64 [n]).  Every track needs the first one's number of frames
+    (ValueError)."""
+    if len(photometries) > 1:
+        raise NotImplementedError("Currently puts all photometries together, can't handle multiple channels at once.")
+    tracks = list(unwind_photometries(photometries))
+    n = len(tracks)
+    F = len(tracks[0][5]) if n else 0
+    if any(len(t[5]) != F or len(t[4]) != F for t in tracks):
+        raise ValueError("every track needs exactly %d intensities and category entries" % F)
+    intensity = np.array([t[5] for t in tracks], dtype=np.float64).reshape(n, F)
+    return (intensity, _tracks.category_words([t[4] for t in tracks], n), np.array([t[1] for t in tracks], dtype=np.int64),
+            np.array([(t[2], t[3]) for t in tracks], dtype=np.int64).reshape(n, 2), np.array([t[6] for t in tracks], dtype=np.int64))
+
+
+def track_table_from_records(records, channel, downstep_filtered=True, channels=None):
+    """track_table_from_photometries(photometries_from_records(records, channel, downstep_filtered, channels)) without the
+    dict: the same table straight from experiment.sequence_experiment_records' output, with array operations only."""
+    from . import experiment as _ex
+    from . import _native_sequence as NQ
+    names = _ex.channel_names(records, channels)
+    C, F = int(records["shape"][1]), int(records["shape"][2])
+    seq, cat = np.asarray(records["trace_seq"]).astype(np.int64), np.asarray(records["category"]).astype(np.uint64)
+    t = np.flatnonzero(_ex._staying(records))
+    # the order of the written file: channels, fields ascending, categories in order of first appearance, traces as tracked
+    _, group = np.unique(np.stack([seq[t].astype(np.uint64), cat[t]]), axis=1, return_inverse=True)
+    group = group.reshape(-1)
+    first = np.full(int(group.max()) + 1 if len(t) else 0, len(seq), np.int64)
+    np.minimum.at(first, group, t)
+    t = t[np.lexsort((t, first[group], seq[t] // C, seq[t] % C))]
+    row = np.arange(1, len(t) + 1, dtype=np.int64)                  # (the header is row 0)
+    mask = np.uint64(0xFFFFFFFFFFFFFFFF) if F >= 64 else np.uint64((1 << F) - 1)
+    word = cat[t] & mask
+    keep = np.isin(seq[t] % C, [c for c in range(C) if names[c] == channel])
+    if downstep_filtered:
+        keep &= ((word & (word + np.uint64(1))) == 0) & ((word & np.uint64(1)) == 1)       # ON in a prefix of the frames, from frame 0
+    t, row, word = t[keep], row[keep], word[keep]
+    have = (np.asarray(records["flags"])[t] & (NQ.DETECTED | NQ.INTERPOLATED)) != 0
+    if len(t) and not have.any(axis=1).all():
+        raise IndexError("index 0 is out of bounds for axis 0 with size 0")      # (a trace without a frame, as the dict route)
+    f0 = np.argmax(have, axis=1)
+    hw = np.asarray(records["hw"])[t, f0].astype(np.int64).reshape(len(t), 2)
+    v = np.where(have, np.asarray(records["photometry"], dtype=np.float64)[t], 0.0)
+    if str(records["photometry_method"]) == 'simple':
+        v = np.trunc(v)
+    intensity = np.where(have, np.where(v >= 0, np.floor(v + 0.5), np.ceil(v - 0.5)), 0.0)         # (_py2_round)
+    field = seq[t] // C
+    # a later track at a (field, h, w) that an earlier one holds is dropped, as the dict's setdefault drops it
+    _, first_at = np.unique(np.stack([field, hw[:, 0], hw[:, 1]]), axis=1, return_index=True)
+    sel = np.sort(first_at)
+    return intensity[sel].reshape(len(sel), F), word[sel], field[sel], hw[sel], row[sel]

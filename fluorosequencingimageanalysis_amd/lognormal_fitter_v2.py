@@ -2,7 +2,8 @@
 fit on the GPU.
 
   python -m fluorosequencingimageanalysis_amd.lognormal_fitter_v2 TRACKS.csv [-c -w -m -o -e -s -n --max_possible
-      --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate --host_bin_search]
+      --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate --host_bin_search
+      --device_chain --no_intermediates]
 
 Steps as there: alpha from the histogram of all photometries, the alpha-adjusted and the truncated dicts, a first beta from
 the last ON frames, a first fit, the ON/OFF adjustment per (cycle, field), a second beta and the second fit.  Written next to
@@ -10,11 +11,18 @@ TRACKS.csv under the reference's names (TRACKS.csv_<hash>_ch<c>_...): COMMANDLIN
 (empty), SIGNALS.pkl and RAW_PHOTOMETRIES.pkl, pickles in protocol 0.  The three plotly HTML files are not built.
 --max_deviation is parsed and, as in the reference, 3 is what the fit gets; -n is accepted and unused.  The histogram bin
 searches behind alpha and both betas run on the GPU where there is one (include/fsq_binsearch.h) and with numpy on the host
-otherwise or with --host_bin_search; the files and the printed text are the same either way."""
+otherwise or with --host_bin_search; the files and the printed text are the same either way.
+
+--device_chain computes the whole chain with lognormal.chain_records: the track table goes to the GPU once and alpha, both
+betas, both fits, the ON/OFF medians, the adjustment and the tally are computed there, with no Python object per track between
+the steps; the files and the printed text are the same again.  INTERMEDIATES_v2.pkl is the one file that holds a tuple per
+track: --no_intermediates leaves it out (on either route), and with it --device_chain builds no per-track tuples at all."""
 import argparse
 import sys
 import time
 from os.path import abspath
+
+import numpy as np
 
 from . import lognormal as _ln
 from .pflib import _epoch_to_hash, _py2_pickle_bytes, _py2_round
@@ -47,6 +55,9 @@ def make_parser():
                    help="Ignore this number of cycles at the beginning when trying to guess the one fluor intensity.")
     p.add_argument('--host_bin_search', action='store_true', default=False,
                    help="Run the histogram bin searches with numpy on the host, not on the GPU.")
+    p.add_argument('--device_chain', action='store_true', default=False,
+                   help="Compute the whole chain on the track table on the GPU (lognormal.chain_records).")
+    p.add_argument('--no_intermediates', action='store_true', default=False, help="Do not write INTERMEDIATES_v2.pkl.")
     return p
 
 
@@ -65,8 +76,62 @@ def _dump(obj, path):
         f.write(_py2_pickle_bytes(obj))
 
 
-def main(argv=None, timestamp_epoch=None, device=None):
-    """Runs the chain; returns a dict of everything it computed (alpha, betas, both fits, the output paths)."""
+def _chain_fit_info(tracks, chain, fit, intensities, max_possible):
+    """photometries_lognormal_fit's all_fit_info of one of chain_records' fits, for INTERMEDIATES_v2.pkl."""
+    host = dict(chain[fit], lengths=np.array([len(t[5]) for t in tracks], dtype=np.int32))
+    fits = _ln._fit_tuples(host, max_possible, lambda i: "track %s field %s (%s, %s)" % tracks[i][:4])
+    return [(channel, field, h, w, row, category, values) + f
+            for (channel, field, h, w, category, _, row), values, f in zip(tracks, intensities, fits)]
+
+
+def _chain_route(args, tracks, device, host):
+    """The chain by lognormal.chain_records: (res, plf_results); all_fit_info is None with --no_intermediates."""
+    if not tracks:
+        raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of no photometries)
+    F = len(tracks[0][5])
+    if any(len(t[5]) != F or len(t[4]) != F for t in tracks):
+        raise ValueError("every track needs exactly %d intensities and category entries" % F)
+    chain = _ln.chain_records([t[5] for t in tracks], [t[4] for t in tracks], [t[1] for t in tracks], args.beta_sigma,
+                              max_possible=args.max_possible, ddif=args.ddif, allow_multidrop=not args.no_multidrop,
+                              truncate=args.truncate, beta=args.beta, no_adjustment=args.no_adjustment, device=device, host=host)
+    signals, all_fit_info = chain["signals"], None
+    if not args.no_intermediates:
+        # the adjusted frames as numpy's float64, the others as the reader's integers: what the dict route pickles
+        scaled = (chain["on_off_count"][chain["segment"]] > 0) | args.no_adjustment
+        intensities = [tuple([x if on else raw for x, on, raw in zip(a[:-1], m, t[5])]) + ((a[-1],) if args.no_adjustment else (t[5][-1],))
+                       for a, m, t in zip(chain["adjusted"], scaled, tracks)]
+        all_fit_info = _chain_fit_info(tracks, chain, "fit1", intensities, args.max_possible)
+        # the same tally from the tuples: its keys are the first tracks' own signal tuples, which the pickle writes once
+        signals, _ = _ln._tracks.tally_signals((f[7], f[8], f[13]) for f in all_fit_info)
+        assert list(signals.items()) == list(chain["signals"].items())
+    return chain, (signals, chain["total_count"], chain["none_count"], all_fit_info)
+
+
+def _write_and_print(args, base, alpha, adj_beta, plf_results, raw_photometries):
+    """The files after COMMANDLINE.pkl and the printed text."""
+    signals = plf_results[0]
+    ddif = tuple([0.0] + [args.ddif] * (args.max_possible + 1))
+    if not args.no_intermediates:
+        # (the two flags that choose the route and this file are left out of the pickled arguments: the file is the same with them)
+        pickled = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ('device_chain', 'no_intermediates')})
+        _dump(((alpha, adj_beta, args.beta_sigma, ddif), plf_results, pickled), base + 'INTERMEDIATES_v2.pkl')
+    open(base + 'CLUSTERED.csv', 'w').close()
+    _dump(signals, base + 'SIGNALS.pkl')
+    print("")
+    print("Signals:")
+    for (signal, is_zero, s_i), count in sorted(signals.items(), key=lambda x: x[0]):
+        print(str((signal, is_zero, s_i)) + "    " + str(count))
+    print("Total number of signals: " + str(sum(signals.values())))
+    print("Total number of signals that fall to 0: " + str(sum([count for (s, z, si), count in signals.items() if z])))
+    print("")
+    _dump(raw_photometries, base + 'RAW_PHOTOMETRIES.pkl')
+    for what in ("histogram", "single drops heatmap", "double drops heatmap"):
+        print("Error saving " + what + " using plotting.py functions. Exception: the plotly HTML files are not built here")
+
+
+def main(argv=None, timestamp_epoch=None, device=None, host=False):
+    """Runs the chain; returns a dict of everything it computed (alpha, betas, both fits, the output paths).  host: with
+    --device_chain, lognormal.chain_records' host=True (numpy on the host, no GPU)."""
     argv = list(sys.argv if argv is None else argv)
     args = make_parser().parse_args(argv[1:])
     tracks_filepath = abspath(args.tracks[0])
@@ -82,6 +147,13 @@ def main(argv=None, timestamp_epoch=None, device=None):
                                                                      downstep_filtered=True, channels=[channel])
     tracks = list(_ln.unwind_photometries(photometries))
     raw_photometries = tuple([i for t in tracks for i in t[5]])
+    if args.device_chain:
+        chain, plf_results = _chain_route(args, tracks, device, host)
+        res = dict(alpha=chain["alpha"], original_beta=chain["original_beta"], original_beta_sigma=chain["original_beta_sigma"],
+                   adj_beta=chain["adj_beta"], adj_beta_sigma=chain["adj_beta_sigma"], chain=chain, plf_results=plf_results,
+                   output_filepath_base=base, args=args)
+        _write_and_print(args, base, chain["alpha"], chain["adj_beta"], plf_results, raw_photometries)
+        return res
     search_device = _search_device(args, device)
     alpha = _ln._get_m0Dm1(raw_photometries=raw_photometries, optimal_bin_number=None, device=search_device)[7]
     alpha_adjusted, truncated = {}, {}
@@ -108,19 +180,7 @@ def main(argv=None, timestamp_epoch=None, device=None):
     plf_results = (signals, total_count, none_count, all_fit_info) = \
         _ln.photometries_lognormal_fit(photometries=adj_photometries, beta=adj_beta, **fit_kw)
 
-    _dump(((alpha, adj_beta, args.beta_sigma, ddif), plf_results, args), base + 'INTERMEDIATES_v2.pkl')
-    open(base + 'CLUSTERED.csv', 'w').close()
-    _dump(signals, base + 'SIGNALS.pkl')
-    print("")
-    print("Signals:")
-    for (signal, is_zero, s_i), count in sorted(signals.items(), key=lambda x: x[0]):
-        print(str((signal, is_zero, s_i)) + "    " + str(count))
-    print("Total number of signals: " + str(sum(signals.values())))
-    print("Total number of signals that fall to 0: " + str(sum([count for (s, z, si), count in signals.items() if z])))
-    print("")
-    _dump(raw_photometries, base + 'RAW_PHOTOMETRIES.pkl')
-    for what in ("histogram", "single drops heatmap", "double drops heatmap"):
-        print("Error saving " + what + " using plotting.py functions. Exception: the plotly HTML files are not built here")
+    _write_and_print(args, base, alpha, adj_beta, plf_results, raw_photometries)
     return dict(alpha=alpha, original_beta=original_beta, original_beta_sigma=original_beta_sigma, adj_beta=adj_beta,
                 adj_beta_sigma=adj_beta_sigma, on_offs=on_offs, adj_photometries=adj_photometries,
                 original_plf_results=original_plf_results, plf_results=plf_results, output_filepath_base=base, args=args)
