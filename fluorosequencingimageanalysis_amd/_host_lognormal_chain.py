@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from . import _host_lognormal
+from . import _host_lognormal_dp
 from . import _tracks
 
 MAX_FRAMES = 64
@@ -130,12 +131,23 @@ def last_drops(rows, bits, truncate=0):
     return np.array([math.log(x) for x in rows[:, :-1][take].tolist()], dtype=np.float64)
 
 
-def fit_rows(rows, bits, log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget):
-    """lognormal.lognormal_device's dict as arrays, with _host_lognormal.fit."""
+def fit_rows(rows, bits, log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget, solver='enumerate'):
+    """lognormal.lognormal_device's dict as arrays, with _host_lognormal.fit, or with solver='dp' _host_lognormal_dp.fit
+    (no track over the budget)."""
     n, F = rows.shape
     out = {"status": np.zeros(n, np.int32), "best_seq": np.zeros((n, F), np.uint8), "best_score": np.full(n, -1.0),
            "frame_score": np.zeros((n, F)), "n_surviving": np.zeros(n, np.int64)}
+    if solver == 'dp':
+        _host_lognormal_dp.check_overflow(beta_sigma, F)
     for t, (I, c) in enumerate(zip(rows.tolist(), bits.tolist())):
+        if solver == 'dp':
+            seq, score, scores, out["n_surviving"][t] = _host_lognormal_dp.fit(I, c, log_fluor_means, beta_sigma, max_possible,
+                                                                               allow_multidrop, max_deviation)
+            if seq is None:
+                out["status"][t] = STATUS_NONE
+            else:
+                out["best_seq"][t], out["best_score"][t], out["frame_score"][t] = seq, score, scores
+            continue
         ok, _ = _host_lognormal.tables(I, c, log_fluor_means, beta_sigma, max_possible, max_deviation)
         out["n_surviving"][t] = min(_host_lognormal.count_surviving(ok, max_possible, allow_multidrop), np.iinfo(np.int64).max)
         if out["n_surviving"][t] > budget:
@@ -180,16 +192,16 @@ def on_off_adjust(rows, seg_off, alpha, m, counts, M):
 
 
 def chain(rows, cats, seg_off, beta_sigma, max_possible=5, ddif=0.30, allow_multidrop=True, truncate=0, beta=None,
-          no_adjustment=False, budget=1 << 22):
+          no_adjustment=False, budget=1 << 22, solver='enumerate'):
     """lognormal.chain_device's dict as NumPy arrays and Python scalars: rows float64 [n, F], cats uint64 [n], seg_off int64
-    [S + 1], the tracks of a field contiguous."""
+    [S + 1], the tracks of a field contiguous.  solver: 'enumerate' or 'dp', the fit of fit_rows."""
     rows = np.ascontiguousarray(rows, dtype=np.float64)
     n, F = rows.shape
     check_frames(F, allow_multidrop)
     seg_off = np.asarray(seg_off, dtype=np.int64)
     bits = category_bits(cats, F)
     quench = tuple([0.0] + [ddif] * (max_possible + 1))
-    fit_kw = dict(beta_sigma=beta_sigma, max_possible=max_possible, allow_multidrop=allow_multidrop, max_deviation=3, budget=budget)
+    fit_kw = dict(beta_sigma=beta_sigma, max_possible=max_possible, allow_multidrop=allow_multidrop, max_deviation=3, budget=budget, solver=solver)
 
     alpha, n_bins = alpha_of_values(rows)
     original_beta, original_beta_sigma = beta_of_values(last_drops(rows, bits, truncate))

@@ -15,10 +15,15 @@ is made per track.  `chain_records(host=True)` is its NumPy twin (_host_lognorma
 
 Limits of the device fit, each raised on the host before anything is launched: 1 .. 64 frames per track
 (NotImplementedError above 64, ValueError for none), max_possible in 1 .. 15 (NotImplementedError above), beta_sigma finite
-and > 0, max_deviation not NaN, finite intensities and finite log_fluor_means (ValueError); allow_upsteps=True is not built
-(NotImplementedError; the command line never passes it).  A track with more surviving sequences than `budget` (default 2^22)
+and > 0, max_deviation not NaN, finite intensities and finite log_fluor_means (ValueError).  With the default solver='enumerate' allow_upsteps=True raises
+NotImplementedError (the command line never passes it), and a track with more surviving sequences than `budget` (default 2^22)
 is not enumerated: it comes back with STATUS_OVER_BUDGET from the array interfaces and raises NotImplementedError naming the
 track from the dict interfaces.
+
+solver='dp' (include/fsq_lognormal_dp.h, _host_lognormal_dp.py) finds the same winner, bit for bit and with the reference's tie
+rule, by an exact dynamic programme in O(frames * max_possible^2) per track: no track is over a budget (`budget` is accepted
+and unused) and allow_upsteps=True is served.  It refuses (ValueError, before any launch) a beta_sigma so small that a product
+of max_frames densities could overflow: 1 / (sqrt(2 pi) * beta_sigma) > 1 and max_frames * log of it >= 700.
 
 Limits of the device bin search, each raised as ValueError on the host before anything is launched: at least one value, finite
 values, integers of magnitude at most 2^53 (beyond it float64 does not hold them), bin counts in 1 .. 10 000
@@ -31,9 +36,11 @@ from math import log, sqrt
 import numpy as np
 
 from . import _host_lognormal_chain as HC
+from . import _host_lognormal_dp as HD
 from . import _native_binsearch as NB
 from . import _native_lognormal as NL
 from . import _native_lognormal_chain as NC
+from . import _native_lognormal_dp as ND
 from . import _tracks
 from . import engine as _engine
 from ._tracks import category_word                                # noqa: F401  (its old place)
@@ -46,9 +53,24 @@ MAX_BINS = NB.MAX_BINS
 
 # ---- the device fit ----
 
+SOLVERS = ('enumerate', 'dp')
+
+
 def _no_upsteps(allow_upsteps):
     if allow_upsteps:
-        raise NotImplementedError("allow_upsteps=True is not built")
+        raise NotImplementedError("allow_upsteps=True is not built with solver='enumerate': pass solver='dp'")
+
+
+def _check_solver(solver, allow_upsteps=False):
+    if solver not in SOLVERS:
+        raise ValueError("solver must be 'enumerate' or 'dp', not %r" % (solver,))
+    if solver == 'enumerate':
+        _no_upsteps(allow_upsteps)
+
+
+def _solver_kw(solver, allow_upsteps=False):
+    """The keywords that choose the dynamic programme; none for the default solver."""
+    return {} if solver == 'enumerate' else {"solver": solver, "allow_upsteps": bool(allow_upsteps)}
 
 
 def fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget):
@@ -82,21 +104,26 @@ def fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_d
 
 
 def lognormal_device(d_intensity, d_category, d_len, log_fluor_means, beta_sigma, max_possible=5, allow_multidrop=True,
-                     max_deviation=3, budget=DEFAULT_BUDGET, prm=None):
+                     max_deviation=3, budget=DEFAULT_BUDGET, prm=None, solver='enumerate', allow_upsteps=False):
     """fsq_lognormal_fit on device tensors: float64 [n, max_frames] intensities, int64 [n] categories (bit f set when frame f
     is ON, the uint64 word of sequencing.py) and int32 [n] lengths.  Returns a dict of device tensors: status int32 [n], best_seq
     uint8 [n, max_frames], best_score float64 [n], frame_score float64 [n, max_frames], n_surviving int64 [n].  Enqueued on the
     current stream, not synchronised.  Lengths and intensities are not checked here: a track whose length is not in
-    1 .. max_frames comes back with status 3.  `prm`: the parameters already built by fit_params (the other arguments are then unused)."""
+    1 .. max_frames comes back with status 3.  `prm`: the parameters already built by fit_params (the other arguments are then unused).
+    solver='dp': fsq_lognormal_fit_dp, the same dict; no status is STATUS_OVER_BUDGET, and allow_upsteps is served."""
     torch = _engine._torch()
+    _check_solver(solver, allow_upsteps)
     if prm is None:
         prm = fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
     dev = d_intensity.device
     n, max_frames = int(d_intensity.shape[0]), int(d_intensity.shape[1])
     if max_frames > NL.MAX_FRAMES:
         raise NotImplementedError("tracks are limited to %d frames" % NL.MAX_FRAMES)
-    L = NL.lib()
-    ws_bytes = L.fsq_lognormal_workspace_bytes(n, max_frames)
+    dp = solver == 'dp'
+    if dp:
+        HD.check_overflow(prm.beta_sigma, max_frames)
+    L = ND.lib() if dp else NL.lib()
+    ws_bytes = (L.fsq_lognormal_dp_workspace_bytes if dp else L.fsq_lognormal_workspace_bytes)(n, max_frames)
     if ws_bytes < 0:
         raise ValueError("fsq_lognormal_workspace_bytes: invalid shape")
     if not (d_intensity.is_contiguous() and d_category.is_contiguous() and d_len.is_contiguous()):
@@ -108,9 +135,10 @@ def lognormal_device(d_intensity, d_category, d_len, log_fluor_means, beta_sigma
            "best_score": torch.empty(n, dtype=torch.float64, device=dev),
            "frame_score": torch.empty((n, max_frames), dtype=torch.float64, device=dev),
            "n_surviving": torch.empty(n, dtype=torch.int64, device=dev)}
-    _engine.launch(L.fsq_lognormal_fit, "fsq_lognormal_fit", dev, d_intensity.data_ptr(), d_category.data_ptr(), d_len.data_ptr(), n,
-                   max_frames, ctypes.byref(prm), out["status"].data_ptr(), out["best_seq"].data_ptr(), out["best_score"].data_ptr(),
-                   out["frame_score"].data_ptr(), out["n_surviving"].data_ptr(), None, 0)
+    _engine.launch(L.fsq_lognormal_fit_dp if dp else L.fsq_lognormal_fit, "fsq_lognormal_fit_dp" if dp else "fsq_lognormal_fit", dev,
+                   d_intensity.data_ptr(), d_category.data_ptr(), d_len.data_ptr(), n, max_frames, ctypes.byref(prm),
+                   out["status"].data_ptr(), out["best_seq"].data_ptr(), out["best_score"].data_ptr(), out["frame_score"].data_ptr(),
+                   out["n_surviving"].data_ptr(), *((1 if allow_upsteps else 0,) if dp else ()), None, 0)
     return out
 
 
@@ -146,19 +174,22 @@ def _rows(intensities, categories, lengths):
 
 
 def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_possible=5, allow_multidrop=True,
-                      max_deviation=3, budget=DEFAULT_BUDGET, lengths=None, device=None):
+                      max_deviation=3, budget=DEFAULT_BUDGET, lengths=None, device=None, solver='enumerate', allow_upsteps=False):
     """The fit for many tracks in one launch, as arrays.
 
     intensities  ragged sequences, a float64 [n, max_frames] array or a CUDA tensor of that shape (with `lengths`, or every
                  row full); categories  tuples of booleans, or the uint64 / int64 words as an array or CUDA tensor.
     Returns a dict of NumPy arrays: status (STATUS_FOUND / STATUS_NONE / STATUS_OVER_BUDGET), best_seq uint8 [n, max_frames],
     best_score, frame_score [n, max_frames], n_surviving int64 and lengths.  Rows beyond a track's length, and the rows of
-    a track without a winner, hold count 0, score 0 and best_score -1."""
+    a track without a winner, hold count 0, score 0 and best_score -1.  solver, allow_upsteps: as lognormal_device."""
+    _check_solver(solver, allow_upsteps)
     prm = fit_params(log_fluor_means, beta_sigma, max_possible, allow_multidrop, max_deviation, budget)
     if hasattr(intensities, "is_cuda"):                            # a torch tensor
         torch = _engine._torch()
         d_int = intensities.contiguous()
         n, F = int(d_int.shape[0]), int(d_int.shape[1])
+        if solver == 'dp':
+            HD.check_overflow(prm.beta_sigma, F)
         dev = d_int.device
         d_len = (torch.full((n,), F, dtype=torch.int32, device=dev) if lengths is None
                  else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous())
@@ -173,6 +204,8 @@ def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_
     else:
         rows, cats, lens = _rows(intensities, categories, lengths)
         n = len(lens)
+        if solver == 'dp':
+            HD.check_overflow(prm.beta_sigma, rows.shape[1])
         if n:
             torch = _engine._torch()
             dev = torch.device(device or "cuda")
@@ -181,7 +214,7 @@ def lognormal_records(intensities, categories, log_fluor_means, beta_sigma, max_
     if n == 0:
         return {"status": np.zeros(0, np.int32), "best_seq": np.zeros((0, 1), np.uint8), "best_score": np.zeros(0),
                 "frame_score": np.zeros((0, 1)), "n_surviving": np.zeros(0, np.int64), "lengths": np.zeros(0, np.int32)}
-    out = lognormal_device(d_int, d_cat, d_len, None, None, prm=prm)
+    out = lognormal_device(d_int, d_cat, d_len, None, None, prm=prm, **_solver_kw(solver, allow_upsteps))
     host = _engine.to_host(out)
     host["lengths"] = np.asarray(lens, dtype=np.int32)
     return host
@@ -335,19 +368,20 @@ def _fit_tuples(host, max_possible, what):
 
 def intensities_to_signal_lognormal(intensities, beta, beta_sigma, max_possible=5, allow_multidrop=True, allow_upsteps=False,
                                     max_deviation=3, quench_factor=0, categories=None, log_fluor_boundaries=None,
-                                    log_fluor_means=None, budget=DEFAULT_BUDGET, device=None):
+                                    log_fluor_means=None, budget=DEFAULT_BUDGET, device=None, solver='enumerate'):
     """MCsimlib._intensities_to_signal_lognormal_v8 on the GPU: (signal, is_zero, best_seq, lmii, best_score,
     best_intensity_scores, starting_intensity).  beta, quench_factor and log_fluor_boundaries are accepted and, as in the
-    reference's v8, unused once log_fluor_means is given."""
+    reference's v8, unused once log_fluor_means is given.  allow_upsteps needs solver='dp'; a winner that steps up comes
+    back as (None, None, best_seq, lmii, best_score, best_intensity_scores, best_seq[0]), as there."""
     if categories is None:
         raise ValueError("categories required in v7+")
     if log_fluor_means is None:
         raise ValueError("v8+ requires log_fluor_means to be passed manually")
-    _no_upsteps(allow_upsteps)
+    _check_solver(solver, allow_upsteps)
     if not allow_multidrop and len(intensities) == 1:
         raise ValueError("max() arg is an empty sequence")        # (max(seq_diff) of a one-frame sequence, :5442)
     host = lognormal_records([intensities], [categories], log_fluor_means, beta_sigma, max_possible, allow_multidrop,
-                             max_deviation, budget, device=device)
+                             max_deviation, budget, device=device, **_solver_kw(solver, allow_upsteps))
     return _fit_tuples(host, max_possible, lambda i: "the track")[0]
 
 
@@ -379,19 +413,20 @@ def write_photometries_dict_to_csv(photometries, filepath, dialect='excel'):
 
 def photometries_lognormal_fit(photometries, beta, beta_sigma, max_possible=5, num_processes=None, allow_upsteps=False,
                                allow_multidrop=True, max_deviation=3, quench_factor=0, quench_factors=None,
-                               budget=DEFAULT_BUDGET, device=None):
+                               budget=DEFAULT_BUDGET, device=None, solver='enumerate'):
     """MCsimlib._photometries_lognormal_fit_MP_v8 (:5496-5558) in one launch: (signals, total_count, none_count, all_fit_info),
     tracks in the nested dict's iteration order (insertion order; Python 2's hash order is not reproduced).  num_processes is
-    accepted and unused.  A track over `budget` raises NotImplementedError naming it."""
+    accepted and unused.  A track over `budget` raises NotImplementedError naming it (never with solver='dp', which allow_upsteps
+    needs; a winner that steps up has no signal and counts towards none_count)."""
     if len(photometries) > 1:
         raise NotImplementedError("Currently puts all photometries together, can't handle multiple channels at once.")
     log_fluor_means = _tracks.log_fluor_means(beta, quench_factors, max_possible)
     tracks = list(unwind_photometries(photometries))
-    _no_upsteps(allow_upsteps)
+    _check_solver(solver, allow_upsteps)
     if not allow_multidrop and any(len(t[5]) == 1 for t in tracks):
         raise ValueError("max() arg is an empty sequence")
     host = lognormal_records([t[5] for t in tracks], [t[4] for t in tracks], log_fluor_means, beta_sigma, max_possible,
-                             allow_multidrop, max_deviation, budget, device=device)
+                             allow_multidrop, max_deviation, budget, device=device, **_solver_kw(solver, allow_upsteps))
     fits = _fit_tuples(host, max_possible, lambda i: "track %s field %s (%s, %s)" % tracks[i][:4])
     all_fit_info = [(channel, field, h, w, row, category, intensities) + fit
                     for (channel, field, h, w, category, intensities, row), fit in zip(tracks, fits)]
@@ -701,17 +736,21 @@ def _check_fit_status(fit, what):
 
 
 def chain_device(d_intensity, d_category, d_seg_off, d_field, beta_sigma, max_possible=5, ddif=0.30, allow_multidrop=True,
-                 truncate=0, beta=None, no_adjustment=False, budget=DEFAULT_BUDGET):
+                 truncate=0, beta=None, no_adjustment=False, budget=DEFAULT_BUDGET, solver='enumerate'):
     """lognormal_fitter_v2.main's computation on a track table on the device: float64 [n, F] intensities, 64-bit [n] category
     words, int64 [S + 1] offsets of the fields' contiguous tracks (d_field, the field number per track, is accepted and not
     needed: the segments say it).  Returns a dict: the scalars alpha, n_bins, original_beta, original_beta_sigma, adj_beta and
     adj_beta_sigma, and the device tensors alpha_adjusted [n, F], adjusted [n, F] (the second fit's input), on_off_median and
     on_off_count [S, F - 1], last_beta_median [1] and fit0, fit1 (lognormal_device's dicts).  Only scalars and histograms of at
-    most 10 000 bins cross to the host; where all values of a bin search are equal, that search's values do too."""
+    most 10 000 bins cross to the host; where all values of a bin search are equal, that search's values do too.  solver='dp':
+    both fits by fsq_lognormal_fit_dp, the same outputs and no track over a budget."""
     torch = _engine._torch()
+    _check_solver(solver)
     _check_chain_tensors(d_intensity, d_category, d_seg_off)
     n, F = int(d_intensity.shape[0]), int(d_intensity.shape[1])
     HC.check_frames(F, allow_multidrop)
+    if solver == 'dp':
+        HD.check_overflow(beta_sigma, F)
     dev = d_intensity.device
     if n == 0:
         raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of no photometries)
@@ -722,7 +761,7 @@ def chain_device(d_intensity, d_category, d_seg_off, d_field, beta_sigma, max_po
 
     def fit(d_rows, beta_now, what):
         prm = fit_params(_tracks.log_fluor_means(beta_now, quench, max_possible), beta_sigma, max_possible, allow_multidrop, 3, budget)
-        out = lognormal_device(d_rows, d_category, d_len, None, None, prm=prm)
+        out = lognormal_device(d_rows, d_category, d_len, None, None, prm=prm, **_solver_kw(solver))
         _check_fit_status(out, what)
         return out
 
@@ -784,17 +823,21 @@ def _grouped_by_first_appearance(fields):
 
 
 def chain_records(intensities, categories, fields, beta_sigma, max_possible=5, ddif=0.30, allow_multidrop=True, truncate=0,
-                  beta=None, no_adjustment=False, budget=DEFAULT_BUDGET, device=None, host=False):
+                  beta=None, no_adjustment=False, budget=DEFAULT_BUDGET, device=None, host=False, solver='enumerate'):
     """The chain for a track table on the host, as arrays: intensities, sequences of one length or a [n, F] array; categories,
     tuples of F booleans or the uint64 words; fields, one integer per track.  Tracks may come in any order: they are grouped by
     field, stably, the fields in the order of their first track, and everything per track comes back in the caller's order.
     Returns chain_device's dict as NumPy arrays (fit0 and fit1 dicts of arrays) with field_ids (one per row of on_off_median
     and on_off_count), segment (the row of every track's field), signals, total_count and none_count of the second fit.
-    host=True: with numpy on the host (_host_lognormal_chain), no GPU needed."""
+    host=True: with numpy on the host (_host_lognormal_chain), no GPU needed.  solver='dp': both fits by the dynamic programme
+    (on the host by its twin), the same outputs and no track over a budget."""
+    _check_solver(solver)
     two_d = isinstance(intensities, np.ndarray) and intensities.ndim == 2
     seqs = intensities if two_d else [np.asarray(s, dtype=np.float64).reshape(-1) for s in intensities]
     F = seqs.shape[1] if two_d else len(seqs[0]) if len(seqs) else 1
     HC.check_frames(F, allow_multidrop)
+    if solver == 'dp':
+        HD.check_overflow(beta_sigma, F)
     rows, _ = _tracks.pack_rows(seqs, width=F, width_error="every track needs exactly %d intensities" % F)
     n = len(rows)
     if not np.isfinite(rows).all():
@@ -806,7 +849,7 @@ def chain_records(intensities, categories, fields, beta_sigma, max_possible=5, d
     if n == 0:
         raise ValueError("min() arg is an empty sequence")         # (optimal_bin_size's min() of no photometries)
     kw = dict(beta_sigma=beta_sigma, max_possible=max_possible, ddif=ddif, allow_multidrop=allow_multidrop, truncate=truncate,
-              beta=beta, no_adjustment=no_adjustment, budget=budget)
+              beta=beta, no_adjustment=no_adjustment, budget=budget, **({} if solver == 'enumerate' else {"solver": solver}))
     g_rows, g_cats = np.ascontiguousarray(rows[order]), np.ascontiguousarray(cats[order])
     if host:
         out = HC.chain(g_rows, g_cats, seg_off, **kw)

@@ -3,7 +3,7 @@ fit on the GPU.
 
   python -m fluorosequencingimageanalysis_amd.lognormal_fitter_v2 TRACKS.csv [-c -w -m -o -e -s -n --max_possible
       --max_deviation --ddif --beta_sigma --beta --no_adjustment --no_multidrop --truncate --host_bin_search
-      --device_chain --no_intermediates]
+      --device_chain --no_intermediates --solver {enumerate,dp}]
 
 Steps as there: alpha from the histogram of all photometries, the alpha-adjusted and the truncated dicts, a first beta from
 the last ON frames, a first fit, the ON/OFF adjustment per (cycle, field), a second beta and the second fit.  Written next to
@@ -16,7 +16,10 @@ otherwise or with --host_bin_search; the files and the printed text are the same
 --device_chain computes the whole chain with lognormal.chain_records: the track table goes to the GPU once and alpha, both
 betas, both fits, the ON/OFF medians, the adjustment and the tally are computed there, with no Python object per track between
 the steps; the files and the printed text are the same again.  INTERMEDIATES_v2.pkl is the one file that holds a tuple per
-track: --no_intermediates leaves it out (on either route), and with it --device_chain builds no per-track tuples at all."""
+track: --no_intermediates leaves it out (on either route), and with it --device_chain builds no per-track tuples at all.
+
+--solver dp runs both fits by the exact dynamic programme (include/fsq_lognormal_dp.h) on every route: the files but
+COMMANDLINE.pkl and the printed text are the same, and no track is over a budget."""
 import argparse
 import sys
 import time
@@ -58,6 +61,8 @@ def make_parser():
     p.add_argument('--device_chain', action='store_true', default=False,
                    help="Compute the whole chain on the track table on the GPU (lognormal.chain_records).")
     p.add_argument('--no_intermediates', action='store_true', default=False, help="Do not write INTERMEDIATES_v2.pkl.")
+    p.add_argument('--solver', choices=_ln.SOLVERS, default='enumerate',
+                   help="How the fit finds its winner: by enumerating the surviving sequences, or by dynamic programme.")
     return p
 
 
@@ -74,6 +79,11 @@ def _search_device(args, device):
 def _dump(obj, path):
     with open(path, 'wb') as f:
         f.write(_py2_pickle_bytes(obj))
+
+
+def _solver_kw(args):
+    """The keyword that chooses the dynamic programme; none for the default solver."""
+    return {} if args.solver == 'enumerate' else {"solver": args.solver}
 
 
 def _chain_fit_info(tracks, chain, fit, intensities, max_possible):
@@ -93,7 +103,8 @@ def _chain_route(args, tracks, device, host):
         raise ValueError("every track needs exactly %d intensities and category entries" % F)
     chain = _ln.chain_records([t[5] for t in tracks], [t[4] for t in tracks], [t[1] for t in tracks], args.beta_sigma,
                               max_possible=args.max_possible, ddif=args.ddif, allow_multidrop=not args.no_multidrop,
-                              truncate=args.truncate, beta=args.beta, no_adjustment=args.no_adjustment, device=device, host=host)
+                              truncate=args.truncate, beta=args.beta, no_adjustment=args.no_adjustment, device=device, host=host,
+                              **_solver_kw(args))
     signals, all_fit_info = chain["signals"], None
     if not args.no_intermediates:
         # the adjusted frames as numpy's float64, the others as the reader's integers: what the dict route pickles
@@ -112,8 +123,8 @@ def _write_and_print(args, base, alpha, adj_beta, plf_results, raw_photometries)
     signals = plf_results[0]
     ddif = tuple([0.0] + [args.ddif] * (args.max_possible + 1))
     if not args.no_intermediates:
-        # (the two flags that choose the route and this file are left out of the pickled arguments: the file is the same with them)
-        pickled = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ('device_chain', 'no_intermediates')})
+        # (the flags that choose the route, the solver and this file are left out of the pickled arguments: the file is the same with them)
+        pickled = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ('device_chain', 'no_intermediates', 'solver')})
         _dump(((alpha, adj_beta, args.beta_sigma, ddif), plf_results, pickled), base + 'INTERMEDIATES_v2.pkl')
     open(base + 'CLUSTERED.csv', 'w').close()
     _dump(signals, base + 'SIGNALS.pkl')
@@ -167,7 +178,7 @@ def main(argv=None, timestamp_epoch=None, device=None, host=False):
         original_beta = args.beta
     ddif = tuple([0.0] + [args.ddif] * (args.max_possible + 1))
     fit_kw = dict(beta_sigma=args.beta_sigma, max_possible=args.max_possible, allow_upsteps=False,
-                  allow_multidrop=not args.no_multidrop, max_deviation=3, quench_factor=0, quench_factors=ddif, device=device)
+                  allow_multidrop=not args.no_multidrop, max_deviation=3, quench_factor=0, quench_factors=ddif, device=device, **_solver_kw(args))
     original_plf_results = _ln.photometries_lognormal_fit(photometries=alpha_adjusted, beta=original_beta, **fit_kw)
     on_offs = _ln.grab_ON_OFFS(original_plf_results[3], alpha_adjust=0)
     if not args.no_adjustment:
