@@ -52,8 +52,10 @@ krm_tracks(const double* __restrict__ intensity, const u64* __restrict__ categor
             rank += (xg < x || (xg == x && g < lane)) ? 1 : 0;
         }
         const u64 lo = __ballot(live && rank == (F - 1) / 2), hi = __ballot(live && rank == F / 2);
-        double m = __builtin_nan("");                              // (no lane holds a rank among NaNs)
-        if (lo && hi) m = middle_mean(__shfl(x, __ffsll((long long)lo) - 1, WAVE), __shfl(x, __ffsll((long long)hi) - 1, WAVE), F & 1);
+        // a NaN lane ranks 0 and no other lane counts it, so the finite lanes still fill both middle ranks: np.median gives NaN
+        const u64 any_nan = __ballot(live && x != x);
+        double m = __builtin_nan("");
+        if (lo && hi && !any_nan) m = middle_mean(__shfl(x, __ffsll((long long)lo) - 1, WAVE), __shfl(x, __ffsll((long long)hi) - 1, WAVE), F & 1);
         v = (x - m) / m;
     }
     int slot = 0;
