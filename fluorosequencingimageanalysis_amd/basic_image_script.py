@@ -34,9 +34,13 @@ def build_parser(timestamp_datetime):
                    help="Keyword arguments for pflib.find_peptides as a quoted Python dict literal, e.g. "
                         "--parameters=\"{'median_filter_size': 6, 'c_std': 3}\"; whatever is not named keeps its default.")
     p.add_argument('-mc', '--monte_carlo', action='store_true', default=False,
-                   help="Use Monte Carlo method to peakfit (not reproduced on the GPU: find_peptides raises "
-                        "NotImplementedError for every image, which is logged like any per-image failure).")
+                   help="Use Monte Carlo method to peakfit.  The reference draws from an unseeded generator; with --seed the "
+                        "fit runs on the GPU under explicit draws, without it find_peptides raises NotImplementedError for "
+                        "every image, which is logged like any per-image failure.")
     p.add_argument('--N_iter', type=int, nargs=1, default=[10**3], help="Sample count handed to find_peptides together with --monte_carlo.")
+    p.add_argument('--seed', type=int, nargs=1, default=[None],
+                   help="Seed of the Monte-Carlo draws (an extension, 0 .. 2^64 - 1), handed to find_peptides together with "
+                        "--monte_carlo.")
     p.add_argument('-n', '--num_processes', type=int, nargs=1, default=[None],
                    help="Number of processes to use (validated like the reference; the parallel workers here are the "
                         "ranks of the torch.distributed job).")
@@ -79,6 +83,8 @@ def main(argv=None):
             fp_parameters = {}
         fp_parameters.setdefault('fit_type', 'monte_carlo')
         fp_parameters.setdefault('N_iter', args.N_iter[0])
+        if args.seed[0] is not None:
+            fp_parameters.setdefault('seed', args.seed[0])
     target_images = find_target_images(target_directories)
     if world > 1:               # one file list and one timestamp for every rank
         import torch.distributed as dist

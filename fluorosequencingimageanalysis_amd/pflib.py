@@ -114,10 +114,32 @@ def _2d_gaussian_function(H, A, h_0, w_0, sigma_h, sigma_w, theta, h, w):
     return A * np.exp(-np.divide(a + b, 2 * sigma_h ** 2)) + H
 
 
-def _fit_2d_gaussian_monte_carlo(subimage, N_iter=10**3):
-    """pflib.py:117-177 draws N_iter parameter sets from numpy's global, unseeded random state and keeps the best: its output
-    differs from run to run in the reference itself, so there is nothing to reproduce."""
-    raise NotImplementedError("fit_type='monte_carlo' draws from an unseeded RNG in the reference (pflib.py:117-177) and is not reproduced")
+_MC_NEEDS_SEED = ("fit_type='monte_carlo' draws from an unseeded RNG in the reference (pflib.py:117-177): pass seed= to run it "
+                  "under this library's explicit draws (DESIGN.md 4.22)")
+
+
+def _fit_2d_gaussian_monte_carlo(subimage, N_iter=10**3, seed=None, candidate=(0, 0)):
+    """Monte-Carlo fit of a circular Gaussian to a 5x5 area -> (h_0, w_0, H, A, sigma_h, sigma_w, theta, fit_img), the
+    reference's tuple with its types and its quirks (fit_img is the LAST iteration's image).  Reference pflib.py:117-177.
+    The reference draws from numpy's global, unseeded state; here the draws are Philox blocks keyed by `seed` and counted by
+    (iteration, pixel, field) = (i, candidate[0], candidate[1]) (an extension), and everything computed from
+    them has the reference's bits.  Without a seed there is nothing to reproduce: NotImplementedError.  Raises the reference's
+    IndexError (no pixel equals the maximum: a NaN ROI) and UnboundLocalError (no iteration improved on the start value)."""
+    if seed is None:
+        raise NotImplementedError(_MC_NEEDS_SEED)
+    from . import _host_montecarlo as _hmc
+    from . import montecarlo as _mc
+    subimage = np.asarray(subimage)
+    assert subimage.shape[0] == 5 and subimage.shape[1] == 5
+    roi = np.asarray(subimage, dtype=np.float64)
+    if int(N_iter) <= 0:                    # (the loop never runs: pflib.py:127-128 may still raise, then :176 does)
+        _mc.check_args(1, seed)
+        _hmc.raise_for(_hmc.NO_MAXIMUM if not (np.max(roi) == roi).any() else _hmc.NEVER_IMPROVED)
+    with _CACHE_LOCK:
+        r = _mc.fit_rois(roi.reshape(1, 25), np.array([[candidate[0], candidate[1]]], np.uint32), N_iter, seed)
+    _hmc.raise_for(int(r["status"][0]))
+    row = r["rows"][0]
+    return (row["p2"], row["p3"], row["H"], row["A"], row["sigma_h"], row["sigma_w"], row["theta"], r["fit"][0].reshape(5, 5))
 
 
 def _fit_2d_gaussian(subimage, implementation='agpy'):
@@ -643,7 +665,8 @@ def _solver_mode(solver):
 
 def find_peptides_batch(images, median_filter_size=5, correlation_matrix=default_correlation_matrix,
                         candidate_pixels=None, c_std=2, r_2_threshold=0.7, consolidation_radius=4,
-                        fit_type='gauss', N_iter=10**3, engine=None, errors='raise', on_chunk=None, solver='reference'):
+                        fit_type='gauss', N_iter=10**3, engine=None, errors='raise', on_chunk=None, solver='reference', seed=None,
+                        first_field=0):
     """find_peptides over a stack uint16[n, H, W] -> list of n dicts.
 
     The stack is streamed through the GPU in chunks of about CHUNK_PIXELS pixels (engine.StreamPipeline: continuous
@@ -653,13 +676,26 @@ def find_peptides_batch(images, median_filter_size=5, correlation_matrix=default
     solver (an extension; the reference has one solver): 'reference' - mpfit as the reference runs it, bit for bit (default);
     'textbook' - the same with MINPACK's qrsolv; 'textbook_f32' - the opt-in single-precision approximation of
     BASELINE configs[4] (csrc/fsq_fit_f32.h: NOT the reference's numbers - 61 % of its kept fits lie within 1e-4 of the fp64
-    solver, 80 % within 1e-3, parity unpinned: configs[4]'s "fp32 LM accumulate" is not met as a parity path)."""
+    solver, 80 % within 1e-3, parity unpinned: configs[4]'s "fp32 LM accumulate" is not met as a parity path).
+    fit_type='monte_carlo' with seed= (an extension: the reference is unseeded, without a seed NotImplementedError): N_iter
+    random trials per candidate under explicit draws counted by (iteration, pixel, first_field + index in the stack), a plain loop
+    over chunks; errors='return' also puts a field's IndexError / UnboundLocalError in its place."""
     mode = _solver_mode(solver)
     if consolidation_radius < 2:
         raise ValueError("consolidation_radius must be at least 2")                # pflib.py:431-432
     if fit_type != 'gauss':
-        raise NotImplementedError("fit_type='monte_carlo' draws from an unseeded RNG in the reference "
-                                  "(pflib.py:117-177) and is not reproduced")
+        if fit_type != 'monte_carlo' or seed is None:
+            raise NotImplementedError(_MC_NEEDS_SEED)
+        rec, counts, fmt = find_peptides_records(images, median_filter_size, correlation_matrix, c_std, r_2_threshold,
+                                                 consolidation_radius, fit_type=fit_type, N_iter=N_iter, seed=seed, first_field=first_field)
+        out = records_to_dicts(rec, counts, fmt, fit_type=fit_type)
+        if on_chunk is not None and out:
+            on_chunk(0, out)
+        if errors == 'raise':
+            for d in out:
+                if isinstance(d, Exception):
+                    raise d
+        return out
     # (candidate_pixels: "Not yet implemented" in the reference, pflib.py:374 - accepted and ignored there and here)
     imgs, fmt = _engine.as_pixel_fields(images)            # integer dtypes, floats holding integer values, or float16
     prm = _engine.detect_params(median_filter_size, correlation_matrix, c_std, fmt)   # (PIXELS_U32: pixel_bits per chunk / small pass)
@@ -697,19 +733,25 @@ def find_peptides_batch(images, median_filter_size=5, correlation_matrix=default
 
 
 def find_peptides_records(images, median_filter_size=5, correlation_matrix=default_correlation_matrix, c_std=2,
-                          r_2_threshold=0.7, consolidation_radius=4, solver='reference', device=False, wide=None, **unused):
+                          r_2_threshold=0.7, consolidation_radius=4, solver='reference', device=False, wide=None, fit_type='gauss',
+                          N_iter=10**3, seed=None, first_field=0, **unused):
     """find_peptides over a stack, results as the byte tables the multi-GPU gather ships instead of dicts:
     -> (records uint8[k, engine.peak_record_bytes(pixel format)] of all fields in order, int32[n] peaks per field (-1: the re-key
     assertion of pflib.py:518 fired for that field), pixel format).  records_to_dicts turns them into find_peptides' dicts.
     device=True: the records are returned as a torch uint8 tensor in HBM (never copied to the host).
     wide=True: integer pixels are worked as uint32 (428-byte records) even when every value fits 16 bits - for callers whose
-    parts must agree on one record format (the ranks of find_peptides_sharded)."""
+    parts must agree on one record format (the ranks of find_peptides_sharded).
+    fit_type='monte_carlo' with seed= (see find_peptides_batch): 16-bit pixels only; the counts also say which exception a
+    field raised (montecarlo.encode_counts: -2 UnboundLocalError, -3 IndexError) and records_to_dicts needs fit_type= to
+    rebuild the normalised sub_img."""
     mode = _solver_mode(solver)
     if consolidation_radius < 2:
         raise ValueError("consolidation_radius must be at least 2")
-    if unused.get("fit_type", "gauss") != 'gauss':
-        raise NotImplementedError("fit_type='monte_carlo' draws from an unseeded RNG in the reference "
-                                  "(pflib.py:117-177) and is not reproduced")
+    if fit_type != 'gauss':
+        if fit_type != 'monte_carlo' or seed is None:
+            raise NotImplementedError(_MC_NEEDS_SEED)
+        return _find_peptides_records_mc(images, median_filter_size, correlation_matrix, c_std, r_2_threshold, consolidation_radius,
+                                         N_iter, seed, first_field, bool(device))
     imgs, fmt = _engine.as_pixel_fields(images, wide=bool(wide))
     is_wide = fmt == N.PIXELS_U32
     if is_wide and mode == N.MODE_TEXTBOOK_F32:
@@ -730,9 +772,53 @@ def find_peptides_records(images, median_filter_size=5, correlation_matrix=defau
     return rec, counts, fmt
 
 
-def records_to_dicts(records, counts, pixel_format=N.PIXELS_U16):
-    """The inverse packaging of find_peptides_records: -> list of dicts (AssertionError instances for failed fields)."""
+def _find_peptides_records_mc(images, median_filter_size, correlation_matrix, c_std, r_2_threshold, consolidation_radius, N_iter,
+                              seed, first_field, device):
+    """find_peptides_records for fit_type='monte_carlo': a plain loop over chunks of CHUNK_PIXELS through fsq_find_peptides_mc
+    (montecarlo.find_peptides_stack) - not the fit queue: a fixed trip count per candidate has no tail to hide."""
+    from . import montecarlo as _mc
+    imgs, fmt = _engine.as_pixel_fields(images)
+    if fmt != N.PIXELS_U16:
+        raise NotImplementedError("fit_type='monte_carlo' takes 16-bit integer pixels only")
+    prm = _engine.detect_params(median_filter_size, correlation_matrix, c_std, fmt)
+    if imgs.ndim != 3:
+        raise ValueError("images must have shape (n, H, W)")
+    n, H, W = imgs.shape
+    _mc.check_args(N_iter, seed, first_field, n)
+    if n == 0 or H < 5 or W < 5:
+        if device:
+            torch = _engine._torch()
+            return torch.zeros((0, _engine.PEAK_RECORD_BYTES), dtype=torch.uint8, device="cuda"), np.zeros(n, np.int32), fmt
+        return np.zeros((0, _engine.PEAK_RECORD_BYTES), np.uint8), np.zeros(n, np.int32), fmt
+    n_chunks = max(1, -(-(n * H * W) // CHUNK_PIXELS))
+    per = -(-n // n_chunks)
+
+    def build():
+        r = _mc.McPathRunner(per, H, W)
+        r.lock = threading.Lock()
+        return r
+    runner = _cached(("mc", _device_key(), per, H, W), build)
+    with runner.lock:
+        rec, counts = _mc.find_peptides_stack(imgs, prm, r_2_threshold, consolidation_radius, int(N_iter), int(seed), int(first_field),
+                                              per, runner, PY2_ROUND, device)
+    return rec, counts, fmt
+
+
+def records_to_dicts(records, counts, pixel_format=N.PIXELS_U16, fit_type='gauss'):
+    """The inverse packaging of find_peptides_records: -> list of dicts (AssertionError instances for failed fields).
+    fit_type='monte_carlo': sub_img is the normalised float ROI the reference fits (pflib.py:446-447), rebuilt from the
+    records' pixel words, and a failed field gives the exception its count stands for (montecarlo.field_exception)."""
     counts = np.asarray(counts).reshape(-1)
+    if fit_type == 'monte_carlo':
+        from . import montecarlo as _mc
+        offs = np.concatenate([[0], np.cumsum(np.maximum(counts, 0))])
+        rows, fit, sub = _engine.split_peak_records(np.asarray(records), pixel_format)
+        out = _records_to_dicts_py(rows, fit, _mc.float_sub_images(sub), offs)
+        for f in np.nonzero(counts < 0)[0]:
+            out[int(f)] = _mc.field_exception(int(f), int(counts[f]))
+        return out
+    if fit_type != 'gauss':
+        raise NotImplementedError("fit_type must be 'gauss' or 'monte_carlo'")
     failed = set(int(k) for k in np.nonzero(counts < 0)[0])
     offs = np.concatenate([[0], np.cumsum(np.maximum(counts, 0))])
     return _records_to_dicts(_engine.peak_record_view(records, pixel_format), None, None, offs, failed, pixel_format)
@@ -756,15 +842,17 @@ def count_candidates(images, median_filter_size=5, correlation_matrix=default_co
 
 def find_peptides(image, median_filter_size=5, correlation_matrix=default_correlation_matrix,
                   candidate_pixels=None, c_std=2, r_2_threshold=0.7, consolidation_radius=4, fit_type='gauss',
-                  N_iter=10**3):
+                  N_iter=10**3, seed=None, first_field=0):
     """Find labeled peptides in a TIRF image and characterise their PSFs.  Reference pflib.py:284-520.
 
-    Returns {(round(h_0), round(w_0)): (h_0, w_0, H, A, sigma_h, sigma_w, theta, sub_img, fit_img, rmse, r_2, s_n)}."""
+    Returns {(round(h_0), round(w_0)): (h_0, w_0, H, A, sigma_h, sigma_w, theta, sub_img, fit_img, rmse, r_2, s_n)}.
+    seed / first_field (an extension): fit_type='monte_carlo' runs under explicit draws keyed by `seed` and counted by
+    (iteration, pixel, first_field); without a seed it raises NotImplementedError (the reference's generator is unseeded)."""
     image = np.asarray(image)
     if image.ndim != 2:
         raise ValueError("image must be two-dimensional")
     return find_peptides_batch(image[None], median_filter_size, correlation_matrix, candidate_pixels, c_std,
-                               r_2_threshold, consolidation_radius, fit_type, N_iter)[0]
+                               r_2_threshold, consolidation_radius, fit_type, N_iter, seed=seed, first_field=first_field)[0]
 
 
 # ---- output naming / on-disk formats (reference pflib.py:523-746) --------------------------------
@@ -1186,13 +1274,13 @@ def _save_job(psfs, converted, timestamp_epoch):
         return None, _portable_error(e)
 
 
-def _save_records_job(blob, pixel_format, converted, timestamp_epoch):
+def _save_records_job(blob, pixel_format, converted, timestamp_epoch, fit_type='gauss'):
     """(worker process or inline) The peak records of ONE image (bytes of uint8[k, engine.PEAK_RECORD_BYTES], as the GPU wrote
     them) -> the reference's dict (built HERE, not in the process that drives the GPU) -> pickle and CSV, then the PNG overlay
     last, so that a reader of the pickles never waits for the cosmetics.  -> ((pkl, csv, png) paths, None) or (None, exception)."""
     try:
         rec = np.frombuffer(blob, dtype=np.uint8).reshape(-1, _engine.PEAK_RECORD_BYTES)
-        psfs = records_to_dicts(rec, [len(rec)], pixel_format)[0]
+        psfs = records_to_dicts(rec, [len(rec)], pixel_format, fit_type)[0]
         pkl = save_psfs_pkl(psfs, image_path=converted, timestamp_epoch=timestamp_epoch)
         tab = save_psfs_csv(psfs, image_path=converted, timestamp_epoch=timestamp_epoch)
         png = save_psfs_png(psfs, image_path=converted, timestamp_epoch=timestamp_epoch)
@@ -1322,15 +1410,25 @@ def image_batch(image_paths, find_peptides_parameters=None, timestamp_epoch=None
     # (round 3 built the dicts here and pickled every one of them into a worker's pipe: 57 images/s).
     for shape, members in _windows(paths, unreadable, pool):
         err, rec, counts, fmt = None, None, None, N.PIXELS_U16
+        fit_type = find_peptides_parameters.get("fit_type", "gauss")
         _join_gpu_warmup()
         try:
             _check_find_peptides_parameters(find_peptides_parameters)
-            rec, counts, fmt = find_peptides_records(np.stack([a for _, _, a in members]), **find_peptides_parameters)
+            if fit_type == 'monte_carlo':
+                # every image is its own find_peptides call, as in the reference's loop (pflib.py:957): its draws are counted by
+                # first_field, not by its place in a window, so a file's result does not depend on the files around it
+                parts = [find_peptides_records(a[None], **find_peptides_parameters) for _, _, a in members]
+                rec, counts, fmt = np.concatenate([q[0] for q in parts]), np.concatenate([q[1] for q in parts]), parts[0][2]
+            else:
+                rec, counts, fmt = find_peptides_records(np.stack([a for _, _, a in members]), **find_peptides_parameters)
             offs = np.concatenate([[0], np.cumsum(np.maximum(counts, 0))])
         except Exception as e:      # noqa: BLE001 - parameter errors etc. hit every image of the window
             err = e
         for m, (ap, converted, _) in enumerate(members):
             e = err
+            if e is None and counts[m] < -1:        # (fit_type='monte_carlo': the field's IndexError / UnboundLocalError)
+                from . import montecarlo as _mc
+                e = _mc.field_exception(m, int(counts[m]))
             if e is None and counts[m] < 0:
                 e = AssertionError("field %d: re-keyed peak collides with an existing key (pflib.py:518)" % m)
             if e is not None:
@@ -1338,10 +1436,10 @@ def image_batch(image_paths, find_peptides_parameters=None, timestamp_epoch=None
                 continue
             blob = rec[offs[m]:offs[m + 1]].tobytes()
             if pool is not None:
-                saving.append((ap, converted, pool.submit("save_records", blob, int(fmt), converted, timestamp_epoch)))
+                saving.append((ap, converted, pool.submit("save_records", blob, int(fmt), converted, timestamp_epoch, fit_type)))
                 reap(8 * _IO_POOL["n"])
             else:
-                saving.append((ap, converted, _save_records_job(blob, int(fmt), converted, timestamp_epoch)))
+                saving.append((ap, converted, _save_records_job(blob, int(fmt), converted, timestamp_epoch, fit_type)))
                 reap(0)
         del rec, members
     reap(0)
@@ -1350,7 +1448,7 @@ def image_batch(image_paths, find_peptides_parameters=None, timestamp_epoch=None
 
 
 _FIND_PEPTIDES_KEYWORDS = ("median_filter_size", "correlation_matrix", "candidate_pixels", "c_std", "r_2_threshold",
-                           "consolidation_radius", "fit_type", "N_iter")
+                           "consolidation_radius", "fit_type", "N_iter", "seed", "first_field")
 
 
 def _check_find_peptides_parameters(fp):
