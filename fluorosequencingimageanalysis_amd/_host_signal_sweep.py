@@ -1,0 +1,257 @@
+"""The host twin of the simulation parameter sweep (include/fsq_signal_sweep.h), NumPy and plain Python: the 64-bit signal
+key and its codec, the classification and tally of count rows, the key table a scoring call is made over and
+signal_correlation (jupyter_development.py:279-578) for many fit dicts at once, in the kernel's order of operations, so that
+fsq_signal_scores can be compared with it bit for bit.  No GPU and no torch are needed."""
+import math
+
+import numpy as np
+
+MAX_DROPS, MAX_FRAMES, EMPTY, NEVER, MAX_COUNT = 10, 64, 0x400, 0x800, (1 << 31) - 1
+METRICS = ('naive', 'my_euclidean', 'normalized_euclidean', 'my_std_normalized_euclidean', 'my_sim_std_normalized_euclidean',
+           'log_rmsd', 'my_canberra', 'my_chebyshev', 'my_normalized_chebyshev', 'my_std_normalized_chebyshev')
+# signal_correlation's other metrics: the signed and rank forms, the two `matching` forms, and what the reference itself stubs
+OTHER_METRICS = ('pearson', 'euclidean', 'chebyshev', 'canberra', 'matching', 'matching_10p', 'kendalltau', 'scipy_canberra',
+                 'my_weighted_std_normalized_euclidean', 'my_pearson', 'my_kendalltau', 'my_spearman_rho')
+NORMALIZE_COUNTS, HEATMAP_NORMALIZE_COUNTS = 1, 2
+SCORE_OK, SCORE_EMPTY, SCORE_DIVZERO, SCORE_DOMAIN = 0, 1, 2, 3
+ROW_SIGNAL, ROW_NONE, ROW_UNKEYED = 0, 1, 2
+NO_DROPS = (('A', 0),)
+
+
+# ---- the key ----
+
+def key_of(start, cycles):
+    """The key of a starting count 0 .. 15 and up to MAX_DROPS drop cycles 1 .. 63 in ascending order."""
+    key = int(start)
+    for i, c in enumerate(cycles):
+        key |= int(c) << (4 + 6 * i)
+    return key
+
+
+def key_of_signal(signal):
+    """The key of the reference's (decrements, is_zero, start), or None where no count row has that signal or it has no key:
+    a letter other than 'A', cycles that do not ascend within 1 .. 63, more than MAX_DROPS or more than `start` drops, a
+    start outside 0 .. 15, an is_zero that is not (drops == start)."""
+    try:
+        s, z, start = signal
+        s = tuple(s)
+        cycles = [] if s == NO_DROPS else [c for _, c in s]
+        if any(a != 'A' for a, _ in s) or int(start) != start or not 0 <= start <= 15 or len(cycles) > min(MAX_DROPS, start):
+            return None
+        if any(int(c) != c or not 1 <= c < MAX_FRAMES for c in cycles) or any(a > b for a, b in zip(cycles, cycles[1:])):
+            return None
+        if not s or bool(z) != (len(cycles) == start) or not isinstance(z, (bool, np.bool_)):
+            return None
+    except (TypeError, ValueError):
+        return None
+    return key_of(start, cycles)
+
+
+def signal_of_key(key):
+    """(decrements, is_zero, start) of a key: what lognormal.signal_of and _tracks.decrements_of_row give for its rows."""
+    key = int(key) & 0xffffffffffffffff                         # (a key read from an int64 tensor may come signed)
+    start, cycles = key & 15, []
+    for i in range(MAX_DROPS):
+        c = (key >> (4 + 6 * i)) & 63
+        if c == 0:
+            if key >> (4 + 6 * i):
+                raise ValueError("0x%x is not a signal key" % key)
+            break
+        cycles.append(c)
+    if len(cycles) > start or any(a > b for a, b in zip(cycles, cycles[1:])):
+        raise ValueError("0x%x is not a signal key" % key)
+    return (tuple(('A', c) for c in cycles) or NO_DROPS), len(cycles) == start, start
+
+
+def classify_row(row):
+    """(ROW_SIGNAL, key), (ROW_NONE, None) for a row with an upstep or (ROW_UNKEYED, None) for one with more than MAX_DROPS
+    drops or a start above 15: kss_tally's row_key."""
+    row = [int(c) for c in row]
+    if not 1 <= len(row) <= MAX_FRAMES:
+        raise ValueError("a row has 1 .. %d frames" % MAX_FRAMES)
+    if any(b > a for a, b in zip(row, row[1:])):
+        return ROW_NONE, None
+    cycles = [f for f in range(1, len(row)) for _ in range(row[f - 1] - row[f])]
+    if row[0] > 15 or len(cycles) > MAX_DROPS:
+        return ROW_UNKEYED, None
+    return ROW_SIGNAL, key_of(row[0], cycles)
+
+
+def tally_rows(rows, points, valid, n_points):
+    """fsq_signal_tally on the host: ([{key: count}] per point, none [n_points], unkeyed [n_points])."""
+    tables = [{} for _ in range(n_points)]
+    none, unkeyed = [0] * n_points, [0] * n_points
+    rows = np.asarray(rows, dtype=np.uint8)
+    uniq, inverse = np.unique(rows, axis=0, return_inverse=True) if len(rows) else (rows, np.zeros(0, np.int64))
+    kinds = [classify_row(r) for r in uniq.tolist()]
+    for i, u in enumerate(np.asarray(inverse).reshape(-1).tolist()):
+        k = int(points[i])
+        if (valid is not None and not valid[i]) or not 0 <= k < n_points:
+            continue
+        what, key = kinds[u]
+        if what == ROW_SIGNAL:
+            tables[k][key] = tables[k].get(key, 0) + 1
+        elif what == ROW_NONE:
+            none[k] += 1
+        else:
+            unkeyed[k] += 1
+    return tables, none, unkeyed
+
+
+# ---- the key table of a scoring call ----
+
+def ordered_signals(signals):
+    """Signals in the order every sum runs in: ascending key, then those without a key by their repr."""
+    keyed = sorted((key_of_signal(s), s) for s in signals if key_of_signal(s) is not None)
+    return [s for _, s in keyed] + sorted((s for s in signals if key_of_signal(s) is None), key=repr)
+
+
+def check_metric(metric):
+    if metric not in METRICS:
+        raise NotImplementedError(metric) if metric in OTHER_METRICS else ValueError("Invalid metric chosen.")
+    return METRICS.index(metric)
+
+
+def key_table(observed_signals, signals, heatmap_only=True, zero_only=True, exclude_signals=None, select_signals=None,
+              allow_multidrop=False):
+    """What fsq_signal_scores reads about the keys: observed int64 [S], in_observed, admitted, heatmap uint8 [S] for the
+    ordered `signals` (the union of the observed dict's and of every fit dict's), and the std metrics' n."""
+    S = len(signals)
+    observed, in_observed = np.zeros(S, np.int64), np.zeros(S, np.uint8)
+    admitted, heatmap = np.zeros(S, np.uint8), np.zeros(S, np.uint8)
+    for i, sig in enumerate(signals):
+        s, z, si = sig
+        if sig in observed_signals:
+            observed[i], in_observed[i] = _count(observed_signals[sig]), 1
+        single = len(set(s)) == len(s)
+        admitted[i] = ((select_signals is None or sig in select_signals) and (not zero_only or bool(z))
+                       and (not heatmap_only or len(s) in (1, 2)) and (allow_multidrop or single)
+                       and (exclude_signals is None or sig not in exclude_signals))
+        heatmap[i] = bool(z) and len(s) in (1, 2) and single
+    n_observed = sum(_count(n) for (s, z, si), n in observed_signals.items()
+                     if (not zero_only or z) and (allow_multidrop or len(set(s)) == len(s)))
+    if n_observed > MAX_COUNT:
+        raise NotImplementedError("observed counts beyond 2^31 - 1")
+    return {"signals": list(signals), "observed": observed, "in_observed": in_observed, "admitted": admitted, "heatmap": heatmap,
+            "n_observed": int(n_observed)}
+
+
+def _count(n):
+    if int(n) != n or not 0 <= n <= MAX_COUNT:
+        raise NotImplementedError("counts are integers in 0 .. 2^31 - 1, not %r" % (n,))
+    return int(n)
+
+
+def normalization_of(normalize_counts, heatmap_normalize_counts):
+    return (NORMALIZE_COUNTS if normalize_counts else 0) | (HEATMAP_NORMALIZE_COUNTS if heatmap_normalize_counts else 0)
+
+
+def fit_matrix(signals, fit_dicts):
+    """int64 [S][P] of the fit dicts' counts over the ordered signals, and every dict's total [P]."""
+    index = {s: i for i, s in enumerate(signals)}
+    fit = np.zeros((len(signals), len(fit_dicts)), np.int64)
+    for k, d in enumerate(fit_dicts):
+        for s, n in d.items():
+            fit[index[s], k] = _count(n)
+    return fit, fit.sum(axis=0)
+
+
+# ---- the scores ----
+
+def scores(table, fit, fit_total, metric, normalization=0, small_count_cutoff=None, contributions=True):
+    """fsq_signal_scores on the host, operation for operation: (score float64 [P], factor float64 [P], status int32 [P],
+    contributions float64 [S][P] or None), NaN where the kernel writes NaN."""
+    m = check_metric(metric)
+    obs, in_obs, adm, heat = (table[k].tolist() for k in ("observed", "in_observed", "admitted", "heatmap"))
+    S, n_obs = len(obs), table["n_observed"]
+    fit = np.asarray(fit, dtype=np.int64).reshape(S, -1)
+    P = fit.shape[1]
+    score, factor = np.full(P, np.nan), np.full(P, np.nan)
+    status = np.zeros(P, np.int32)
+    contrib = np.full((S, P), np.nan) if contributions else None
+    cutoff = None if small_count_cutoff is None else float(small_count_cutoff)
+    for k in range(P):
+        f_k, n_fit = fit[:, k].tolist(), int(fit_total[k])
+        pairs = [i for i in range(S) if adm[i] and (in_obs[i] or f_k[i] > 0)
+                 and (cutoff is None or (float(obs[i]) >= cutoff and float(f_k[i]) >= cutoff))]
+        sum_o, sum_f = sum(obs[i] for i in pairs), sum(f_k[i] for i in pairs)
+        nf = 1.0
+        if (normalization & NORMALIZE_COUNTS) and pairs and sum_f > 0:
+            nf = float(sum_o) / float(sum_f)
+        elif normalization & HEATMAP_NORMALIZE_COUNTS:
+            hot = [i for i in range(S) if heat[i] and (in_obs[i] or f_k[i] > 0)]
+            heat_o, heat_f = sum(obs[i] for i in hot if in_obs[i]), sum(f_k[i] for i in hot)
+            if heat_f == 0:
+                status[k] = SCORE_DIVZERO
+                continue
+            nf = float(heat_o) / float(heat_f)
+        factor[k] = nf
+        if not pairs:
+            status[k] = SCORE_EMPTY
+            continue
+        acc, n_contrib, divzero, domain = 0.0, 0, False, False
+        for i in pairs:
+            oi, o, f = obs[i], float(obs[i]), float(f_k[i]) * nf
+            is_max = False
+            if m == 0:
+                c = o * f
+            elif m == 1:
+                c = (f - o) ** 2
+            elif m in (2, 8):
+                if oi <= 0:
+                    continue
+                c, is_max = ((f - o) / o) ** 2 if m == 2 else abs(o - f) / o, m == 8
+            elif m in (3, 4, 9):
+                sd = 1.0
+                if m == 4:
+                    if f > 0.0:
+                        v = f * (float(n_fit) - f) / float(n_fit)
+                        if v < 0.0:
+                            domain = True
+                            continue
+                        sd = math.sqrt(v)
+                elif oi > 0:
+                    if n_obs == 0:
+                        divzero = True
+                        continue
+                    v = float(oi * (n_obs - oi)) / float(n_obs)
+                    if v < 0.0:
+                        domain = True
+                        continue
+                    sd = math.sqrt(v)
+                if sd == 0.0:
+                    divzero = True
+                    continue
+                c, is_max = ((f - o) / sd) ** 2 if m != 9 else abs(o - f) / sd, m == 9
+            elif m == 5:
+                c = (math.log(float(oi + 1)) - math.log(f + 1.0)) ** 2
+            elif m == 6:
+                den = abs(o) + abs(f)
+                if den == 0.0:
+                    divzero = True
+                    continue
+                c = abs(o - f) / den
+            else:
+                c, is_max = abs(o - f), True
+            n_contrib += 1
+            if contrib is not None:
+                contrib[i, k] = c
+            acc = max(acc, c) if is_max else acc + c
+        if domain or divzero or (m == 8 and n_contrib == 0):
+            status[k] = SCORE_DIVZERO if divzero and not domain else SCORE_DOMAIN
+            continue
+        score[k] = acc if m in (0, 6, 7, 8, 9) else math.sqrt(acc / float(n_contrib)) if m == 5 else math.sqrt(acc)
+    return score, factor, status, contrib
+
+
+def result_of(signals, score, factor, status, contrib, k):
+    """signal_correlation's return value for point k, or its exception."""
+    st = int(status[k])
+    if st == SCORE_DIVZERO:
+        raise ZeroDivisionError("float division by zero")
+    if st == SCORE_DOMAIN:
+        raise ValueError("signal_correlation: the maximum of no contributions, or the root of a negative variance")
+    if st == SCORE_EMPTY:
+        return None, (float(factor[k]), {})
+    c = {} if contrib is None else {s: float(contrib[i][k]) for i, s in enumerate(signals) if contrib[i][k] == contrib[i][k]}
+    return float(score[k]), (float(factor[k]), c)

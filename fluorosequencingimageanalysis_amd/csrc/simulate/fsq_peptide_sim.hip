@@ -11,11 +11,13 @@
 // The tables a lane fills row by row ([n][frames] counts, intensities, log intensities, [n][labelled] losses) are staged in
 // LDS, row stride odd in banks, and leave as the 64 rows' contiguous span of global memory, consecutive lanes storing
 // consecutive elements.  The per-molecule words (category, Edman failures, draw counts) are stored by their lane.
+// The lane's two steps are in fsq_peptide_lane.h, which the parameter sweep (fsq_signal_sweep.hip) shares.
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_peptide_sim.h"
 #include "../libm/fsq_glibc_log.h"
 #include "fsq_philox.h"
+#include "fsq_peptide_lane.h"
 
 namespace {
 
@@ -23,41 +25,6 @@ constexpr int WAVE = 64;
 constexpr int MAX_BLOCKS = 16384;
 constexpr int LOSS_STRIDE = 20;              // bytes of a lane's loss row in LDS: 5 banks, odd
 
-// The draws of one (molecule, stream) pair in order: a block gives two, the second waits in w2, w3.
-struct Draws {
-    uint32_t k0, k1, mlo, mhi, stream, w2, w3;
-    int j;
-    __device__ __forceinline__ double next()
-    {
-        double r;
-        if ((j & 1) == 0) {
-            const Words w = philox4x32_10((uint32_t)(j >> 1), mlo, mhi, stream, k0, k1);
-            w2 = w.w2; w3 = w.w3;
-            r = uniform53(w.w0, w.w1);
-        } else {
-            r = uniform53(w2, w3);
-        }
-        ++j;
-        return r;
-    }
-};
-
-__device__ __forceinline__ Draws draws_of(unsigned long long seed, unsigned long long molecule, uint32_t stream)
-{
-    Draws d;
-    d.k0 = (uint32_t)seed; d.k1 = (uint32_t)(seed >> 32);
-    d.mlo = (uint32_t)molecule; d.mhi = (uint32_t)(molecule >> 32);
-    d.stream = stream; d.w2 = d.w3 = 0u; d.j = 0;
-    return d;
-}
-
-// LDS row strides for `frames` frames: doubles (odd) and bytes (a multiple of 4 with an odd number of banks)
-__host__ __device__ __forceinline__ int dbl_stride(int frames) { return frames | 1; }
-__host__ __device__ __forceinline__ int cnt_stride(int frames)
-{
-    int s = (frames + 3) / 4;
-    return 4 * (s | 1);
-}
 size_t lds_bytes(int frames)
 {
     return (size_t)WAVE * dbl_stride(frames) * 8 + (size_t)WAVE * cnt_stride(frames) + 2 * (size_t)WAVE * LOSS_STRIDE;
@@ -83,6 +50,7 @@ kps_simulate(const FsqPeptideSimParams prm, const long long n, uint8_t* __restri
     uint8_t* const my_lcau = s_lcau + lane * LOSS_STRIDE;
     double* const my_dbl = s_dbl + lane * DS;
     const unsigned long long labels = prm.label_mask;
+    const LaneChem chem = {prm.p, prm.per_cycle_b, prm.u, prm.s, prm.s2};
 
     for (long long base = (long long)blockIdx.x * WAVE; base < n; base += (long long)gridDim.x * WAVE) {
         const int rows = (int)(n - base < WAVE ? n - base : WAVE);
@@ -93,34 +61,8 @@ kps_simulate(const FsqPeptideSimParams prm, const long long n, uint8_t* __restri
 
         // ---- 1. chemistry --------------------------------------------------------------------------------------------
         if (active) {
-            Draws d0 = draws_of(prm.seed, molecule, 0u);
-            unsigned long long live = labels;
-            int nterm = 0;
-            for (int k = 0; k < L; ++k) { my_lcyc[k] = 0; my_lcau[k] = FSQ_PEPTIDE_CAUSE_NONE; }
-            auto lose = [&](int b, int cycle, int cause) {
-                const int k = __builtin_popcountll(labels & ((1ull << b) - 1ull));
-                my_lcyc[k] = (uint8_t)cycle;
-                my_lcau[k] = (uint8_t)cause;
-                live &= ~(1ull << b);
-            };
-            for (unsigned long long m = labels; m; m &= m - 1ull)                       // dud (:105-120)
-                if (d0.next() < prm.u) lose(__builtin_ctzll(m), 0, FSQ_PEPTIDE_CAUSE_DUD);
-            for (int c = 0; c <= C; ++c) {
-                if (c > prm.num_mocks && nterm < prm.length) {                          // Edman (:47-75)
-                    if (d0.next() < prm.p) {
-                        if ((live >> nterm) & 1ull) lose(nterm, c, FSQ_PEPTIDE_CAUSE_EDMAN);
-                        ++nterm;
-                    } else {
-                        fail |= 1ull << c;
-                    }
-                }
-                if (c > 0 && d0.next() < (c <= prm.sc ? prm.s : prm.s2))                // strip (:153-169)
-                    for (unsigned long long m = live; m; m &= m - 1ull) lose(__builtin_ctzll(m), c, FSQ_PEPTIDE_CAUSE_STRIP);
-                for (unsigned long long m = live; m; m &= m - 1ull)                     // photobleach (:84-99)
-                    if (d0.next() > prm.per_cycle_b) lose(__builtin_ctzll(m), c, FSQ_PEPTIDE_CAUSE_DESTRUCTION);
-                my_cnt[c] = (uint8_t)__builtin_popcountll(live);
-            }
-            n_draws0 = d0.j;
+            n_draws0 = lane_chemistry<true>(chem, prm.seed, molecule, labels, L, prm.length, prm.num_mocks, C, prm.sc, my_cnt, my_lcyc,
+                                            my_lcau, &fail);
         }
         __syncthreads();
         for (int t = lane; t < rows * F; t += WAVE) g_counts[base * F + t] = s_cnt[(t / F) * CS + t % F];
@@ -131,49 +73,12 @@ kps_simulate(const FsqPeptideSimParams prm, const long long n, uint8_t* __restri
 
         // ---- 2. photometry -------------------------------------------------------------------------------------------
         if (active) {
-            Draws d1 = draws_of(prm.seed, molecule, 1u), d2 = draws_of(prm.seed, molecule, 2u);
-            const int c0 = my_cnt[0];
-            unsigned super = 0u;                                                        // bit q: superdye draw q came out true
-            for (int q = 0; q < c0; ++q)
-                if (d1.next() < prm.superdye_rate) super |= 1u << q;
-            const int total = __builtin_popcount(super);
-            unsigned long long category = 0ull;
-            bool has_gauss = false;
-            double gauss = 0.0;
-            int prev = c0;
-            for (int f = 0; f < F; ++f) {
-                const int c = my_cnt[f];
-                double intensity = 0.0;
-                if (c > 0) {
-                    double dyes = (double)c;
-                    if (prm.superdye_rate != 0.0) {
-                        // the draws of the drops before frame f are the first c0 - counts[f - 1]: what is left of `total`
-                        // is the suffix sum of :350-352
-                        const int before = f == 0 ? 0 : c0 - prev;
-                        const int inc = total - __builtin_popcount(super & ((1u << before) - 1u));
-                        dyes = dyes + (double)inc * prm.superdye_factor;
-                    }
-                    const double mean = (prm.log_beta + ln_log(dyes)) - s_ddif[c - 1];
-                    double z;
-                    if (has_gauss) {
-                        z = gauss;
-                        has_gauss = false;
-                    } else {                                                            // numpy's legacy_gauss
-                        int block = d2.j >> 1;
-                        z = polar_pair(&block, d2.mlo, d2.mhi, 2u, d2.k0, d2.k1, &gauss);
-                        d2.j = 2 * block;
-                        has_gauss = true;
-                    }
-                    intensity = fsq_exp(mean + prm.beta_sigma * z);
-                    category |= 1ull << f;
-                }
-                prev = c;
-                my_dbl[f] = intensity;
-            }
+            int n_draws1, n_draws2;
+            const unsigned long long category = lane_photometry(prm, s_ddif, molecule, F, my_cnt, my_dbl, &n_draws1, &n_draws2);
             g_category[base + lane] = category;
             g_edman_fail[base + lane] = fail;
             int32_t* const nd = g_n_draws + (base + lane) * 3;
-            nd[0] = n_draws0; nd[1] = d1.j; nd[2] = d2.j;
+            nd[0] = n_draws0; nd[1] = n_draws1; nd[2] = n_draws2;
         }
         __syncthreads();
         for (int t = lane; t < rows * F; t += WAVE) g_intensity[base * F + t] = s_dbl[(t / F) * DS + t % F];
@@ -197,29 +102,6 @@ __global__ void kps_philox_words(const uint32_t* __restrict__ counters, const ui
                                       keys[2 * i + 1]);
         out[4 * i] = w.w0; out[4 * i + 1] = w.w1; out[4 * i + 2] = w.w2; out[4 * i + 3] = w.w3;
     }
-}
-
-bool is_finite(double x) { return x - x == 0.0; }
-
-bool params_ok(const FsqPeptideSimParams* p, int64_t n)
-{
-    if (!p || n < 0) return false;
-    if (p->length < 1 || p->length > FSQ_PEPTIDE_MAX_LENGTH) return false;
-    if (p->length < 64 && (p->label_mask >> p->length) != 0) return false;
-    const int L = __builtin_popcountll(p->label_mask);
-    if (L > FSQ_PEPTIDE_MAX_LABELLED) return false;
-    if (p->num_mocks < 0 || p->num_edmans < 0 || p->num_mocks > FSQ_PEPTIDE_MAX_FRAMES || p->num_edmans > FSQ_PEPTIDE_MAX_FRAMES ||
-        p->num_mocks + p->num_edmans + 1 > FSQ_PEPTIDE_MAX_FRAMES)
-        return false;
-    if (p->n_ddif < L || p->n_ddif > FSQ_PEPTIDE_MAX_LABELLED) return false;
-    for (int i = 0; i < p->n_ddif; ++i)
-        if (!is_finite(p->ddif[i])) return false;
-    if (!(is_finite(p->p) && is_finite(p->per_cycle_b) && is_finite(p->u) && is_finite(p->s) && is_finite(p->s2) && is_finite(p->log_beta) &&
-          is_finite(p->beta_sigma) && is_finite(p->superdye_factor)))
-        return false;
-    if (!(p->superdye_rate >= 0.0 && p->superdye_rate <= 1.0)) return false;
-    if (p->first_molecule < 0 || n > INT64_MAX - p->first_molecule) return false;
-    return true;
 }
 
 }  // namespace

@@ -1,0 +1,393 @@
+"""Simulation parameter sweeps scored against observed signals on the GPU: the loop of the reference's
+jupyter_development.py that turns simulations into an answer.
+
+There, simulate_peptide.py runs once per point of an (Edman efficiency p, dye destruction b, dud rate u) grid, the pickles are
+collected into all_simulations = {(p, b, u): (signals, molecular_signals)}, and match_diagnostic (:786-948) scores every point
+against the experiment's signals with signal_correlation (:279-578) and takes the best.  Here that is two calls,
+
+    sweep = sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=..., **fixed_parameters)
+    point, result, factor, contributions = best_point(score_records(observed_signals, sweep, metric=...), reverse_order)
+
+and one device path (include/fsq_signal_sweep.h): fsq_peptide_simulate_points simulates every point's molecules in one
+flattened space, lognormal.lognormal_device fits them, fsq_signal_tally counts the molecules' and the fits' signals into one
+hash table per point without leaving the device, fsq_signal_lookup makes the dense count matrix and fsq_signal_scores scores
+all points at once.
+
+`points` are (p, b, u) triples - peptide_simulation's p, b and u - or dicts with those keys and optionally s, s2 or
+per_cycle_b; everything else is fixed_parameters.  Point k simulates molecules first_molecule + k * molecule_stride + i; with
+molecule_stride = 0 every point sees the same draws (common random numbers), and each point's result is then what
+peptide_simulator.simulate_and_fit_records gives for that point alone.
+
+Limits, each an error and never a wrong count: a signal has at most 10 drops and starts at 15 dyes or fewer (the 64-bit key;
+NotImplementedError), a point has at most `table_slots` distinct signals (ValueError naming table_slots=), counts are below 2^31.
+Ten of signal_correlation's metrics are built (METRICS: those whose terms are non-negative sums or maxima); the others raise
+NotImplementedError with the metric's name.  Sums run in ascending key order where the reference's run in dict order: a sum of
+S non-negative terms differs by at most a relative 2 S 2^-53.  best_point's tie rule: the first point in grid order (the
+reference's: its dict order); points without a result (None) are never chosen."""
+import ctypes
+
+import numpy as np
+
+from . import _host_signal_sweep as H
+from . import _native_signal_sweep as NS
+from . import _tracks
+from . import engine as _engine
+from . import peptide_simulator as PS
+
+METRICS = H.METRICS
+_SCORE_KW = ("heatmap_only", "zero_only", "exclude_signals", "select_signals", "allow_multidrop")
+
+
+# ---- points ----
+
+def _point_dict(point):
+    if isinstance(point, dict):
+        return dict(point)
+    p, b, u = point
+    return {"p": p, "b": b, "u": u}
+
+
+def _point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points, fixed):
+    """(the base FsqPeptideSimParams, float64 [P][5] of FsqSweepPoint values, the points as dict keys).  Every point goes through
+    peptide_simulator._params: its checks, and per_cycle_b = e ** -b as a single simulation computes it."""
+    points = list(points)
+    if not points:
+        raise ValueError("at least one point is needed")
+    values, base = np.empty((len(points), 5)), None
+    for k, point in enumerate(points):
+        ep = dict(fixed)
+        ep.update(_point_dict(point))
+        if 'per_cycle_b' in ep and 'b' in _point_dict(point):
+            del ep['per_cycle_b']
+        prm, _ = PS._params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, ep)
+        values[k] = (prm.p, prm.per_cycle_b, prm.u, prm.s, prm.s2)
+        base = base or prm
+    keys = [tuple(sorted(p.items())) if isinstance(p, dict) else tuple(p) for p in points]
+    if len(set(keys)) != len(keys):
+        raise ValueError("a point stands twice")
+    return base, values, keys
+
+
+def _check_sweep_shape(num_simulations, molecule_stride, table_slots, chunk_rows):
+    n, stride, slots, chunk = int(num_simulations), int(molecule_stride), int(table_slots), int(chunk_rows)
+    if n < 1 or stride < 0 or chunk < 1:
+        raise ValueError("num_simulations and chunk_rows must be positive and molecule_stride must not be negative")
+    if slots < 1 or slots & (slots - 1) or slots > NS.MAX_SLOTS:
+        raise ValueError("table_slots=%d must be a power of two up to 2^24" % slots)
+    return n, stride, slots, chunk
+
+
+# ---- the device path ----
+
+def simulate_points_device(prm, d_points, n_points, n_per_point, molecule_stride=0, first_row=0, n_rows=None):
+    """fsq_peptide_simulate_points: counts uint8 [n_rows, frames], intensity float64 [n_rows, frames] and category int64 [n_rows]
+    of rows first_row .. first_row + n_rows - 1 of the flattened [n_points][n_per_point] space; d_points is a float64 CUDA
+    tensor [n_points, 5] of (p, per_cycle_b, u, s, s2).  Enqueued on the current stream, not synchronised."""
+    torch = _engine._torch()
+    if d_points.dtype != torch.float64 or tuple(d_points.shape) != (int(n_points), 5) or not d_points.is_contiguous():
+        raise ValueError("a contiguous float64 tensor [n_points, 5] is needed")
+    n = int(n_points) * int(n_per_point) - int(first_row) if n_rows is None else int(n_rows)
+    dev, F = d_points.device, prm.num_mocks + prm.num_edmans + 1
+    out = {"counts": torch.empty((max(n, 0), F), dtype=torch.uint8, device=dev),
+           "intensity": torch.empty((max(n, 0), F), dtype=torch.float64, device=dev),
+           "category": torch.empty(max(n, 0), dtype=torch.int64, device=dev)}
+    _engine.launch(NS.lib().fsq_peptide_simulate_points, "fsq_peptide_simulate_points", dev, ctypes.byref(prm), d_points.data_ptr(),
+                   int(n_points), int(n_per_point), int(molecule_stride), int(first_row), n,
+                   *[out[k].data_ptr() if out[k].numel() else None for k in ("counts", "intensity", "category")])
+    return out
+
+
+def new_tables(n_points, slots, device):
+    """The empty tables of fsq_signal_tally: keys int64 [n_points, slots] (the uint64 keys' bits), counts int64 [n_points, slots],
+    none and unkeyed int64 [n_points], overflow int32 [n_points]."""
+    torch = _engine._torch()
+    return {"keys": torch.full((n_points, slots), NS.EMPTY, dtype=torch.int64, device=device),
+            "counts": torch.zeros((n_points, slots), dtype=torch.int64, device=device),
+            "none": torch.zeros(n_points, dtype=torch.int64, device=device),
+            "unkeyed": torch.zeros(n_points, dtype=torch.int64, device=device),
+            "overflow": torch.zeros(n_points, dtype=torch.int32, device=device)}
+
+
+def tally_device(tables, d_rows, d_point, d_valid=None):
+    """fsq_signal_tally: adds the signals of uint8 [n, frames] rows to the tables of their points (int32 [n]); d_valid uint8 [n]
+    or None.  Enqueued, not synchronised."""
+    torch = _engine._torch()
+    n, frames = int(d_rows.shape[0]), int(d_rows.shape[1])
+    if d_rows.dtype != torch.uint8 or d_point.dtype != torch.int32 or tuple(d_point.shape) != (n,):
+        raise ValueError("uint8 rows [n, frames] and int32 points [n] are needed")
+    if d_valid is not None and (d_valid.dtype != torch.uint8 or tuple(d_valid.shape) != (n,)):
+        raise ValueError("a uint8 mask [n] is needed")
+    if not 1 <= frames <= NS.MAX_FRAMES:
+        raise ValueError("rows have 1 .. %d frames" % NS.MAX_FRAMES)
+    if not (d_rows.is_contiguous() and d_point.is_contiguous() and (d_valid is None or d_valid.is_contiguous())):
+        raise ValueError("contiguous tensors are needed")
+    n_points, slots = (int(x) for x in tables["keys"].shape)
+    _engine.launch(NS.lib().fsq_signal_tally, "fsq_signal_tally", d_rows.device, d_rows.data_ptr() if n else None, frames,
+                   d_point.data_ptr() if n else None, None if d_valid is None or not n else d_valid.data_ptr(), n, n_points, slots,
+                   tables["keys"].data_ptr(), tables["counts"].data_ptr(), tables["none"].data_ptr(), tables["unkeyed"].data_ptr(),
+                   tables["overflow"].data_ptr())
+
+
+def lookup_device(tables, d_wanted):
+    """fsq_signal_lookup: int64 [n_wanted, n_points] counts of the int64-viewed keys d_wanted in every point's table."""
+    torch = _engine._torch()
+    n_points, slots = (int(x) for x in tables["keys"].shape)
+    if d_wanted.dtype != torch.int64 or d_wanted.dim() != 1 or not d_wanted.is_contiguous():
+        raise ValueError("a contiguous int64 tensor [n_wanted] is needed")
+    out = torch.empty((int(d_wanted.shape[0]), n_points), dtype=torch.int64, device=d_wanted.device)
+    _engine.launch(NS.lib().fsq_signal_lookup, "fsq_signal_lookup", d_wanted.device, tables["keys"].data_ptr(),
+                   tables["counts"].data_ptr(), n_points, slots, d_wanted.data_ptr() if out.numel() else None, int(d_wanted.shape[0]),
+                   out.data_ptr() if out.numel() else None)
+    return out
+
+
+def _check_tables(tables, what, slots):
+    if bool(tables["overflow"].any()):
+        k = int(tables["overflow"].nonzero()[0])
+        raise ValueError("point %d has more distinct %s than table_slots=%d: pass a larger power of two" % (k, what, slots))
+    if bool(tables["unkeyed"].any()):
+        k = int(tables["unkeyed"].nonzero()[0])
+        raise NotImplementedError("point %d has %s with more than %d drops, or that start above 15 dyes: they have no 64-bit key"
+                                  % (k, what, NS.MAX_DROPS))
+
+
+def sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=0, first_molecule=0, molecule_stride=0,
+                 fit=True, max_possible=5, allow_multidrop=True, max_deviation=3, quench_factors=None, solver=None, table_slots=1024,
+                 chunk_rows=1 << 22, device=None, **fixed_parameters):
+    """Simulate num_simulations molecules at every point, drop the molecules without dyes at any frame, fit the rest with
+    lognormal.lognormal_device and tally the molecules' count rows and the fits' best_seq rows per point, in chunks of at most
+    chunk_rows rows (the result does not depend on it).  Returns a dict: `points` (the points as dict keys, in grid order),
+    `molecular` and `signals` (the tables of new_tables; `signals` is None with fit=False), total_count and none_count (int64
+    CUDA tensors [n_points]; as lognormal.photometries_lognormal_fit counts the kept tracks), num_simulations, table_slots."""
+    torch = _engine._torch()
+    from . import lognormal as LN
+    n, stride, slots, chunk = _check_sweep_shape(num_simulations, molecule_stride, table_slots, chunk_rows)
+    base, values, keys = _point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points, fixed_parameters)
+    P, F = len(keys), base.num_mocks + base.num_edmans + 1
+    dev = torch.device(device or "cuda")
+    fit_kw = {}
+    if fit:
+        means = _tracks.log_fluor_means(fixed_parameters['beta'], quench_factors, max_possible)
+        fit_kw = dict(prm=LN.fit_params(means, fixed_parameters['beta_sigma'], max_possible, allow_multidrop, max_deviation,
+                                        LN.DEFAULT_BUDGET), **LN._solver_kw(solver or 'enumerate'))
+        if not allow_multidrop and F == 1:
+            raise ValueError("max() arg is an empty sequence")        # (as lognormal.photometries_lognormal_fit, :5442)
+    d_points = torch.from_numpy(values).to(dev)
+    molecular, signals = new_tables(P, slots, dev), new_tables(P, slots, dev) if fit else None
+    total, found_n = torch.zeros(P, dtype=torch.int64, device=dev), torch.zeros(P, dtype=torch.int64, device=dev)
+    bad = torch.zeros((), dtype=torch.bool, device=dev)
+    for first in range(0, P * n, chunk):
+        rows = min(chunk, P * n - first)
+        sim = simulate_points_device(base, d_points, P, n, stride, first, rows)
+        d_point = torch.div(torch.arange(first, first + rows, device=dev), n, rounding_mode="floor").to(torch.int32)
+        keep = sim["category"] != 0
+        tally_device(molecular, sim["counts"], d_point, keep.to(torch.uint8))
+        if not fit:
+            total += torch.bincount(d_point[keep], minlength=P)
+            continue
+        d_int, d_cat, d_pt = sim["intensity"][keep].contiguous(), sim["category"][keep].contiguous(), d_point[keep].contiguous()
+        kept = int(d_int.shape[0])
+        if not kept:
+            continue
+        d_len = torch.full((kept,), F, dtype=torch.int32, device=dev)
+        out = LN.lognormal_device(d_int, d_cat, d_len, None, None, **fit_kw)
+        found = out["status"] == LN.STATUS_FOUND
+        bad |= (out["status"] > LN.STATUS_NONE).any()
+        tally_device(signals, out["best_seq"], d_pt, found.to(torch.uint8))
+        total += torch.bincount(d_pt, minlength=P)
+        found_n += torch.bincount(d_pt[found], minlength=P)
+    if bool(bad):
+        raise NotImplementedError("a simulated track has more surviving sequences than the budget, or an invalid length")
+    _check_tables(molecular, "molecular signals", slots)
+    if fit:
+        _check_tables(signals, "fitted signals", slots)
+    return {"points": keys, "molecular": molecular, "signals": signals, "total_count": total,
+            "none_count": total - found_n if fit else None, "num_simulations": n, "table_slots": slots}
+
+
+def _decode_tables(tables):
+    """[{signal: count}] per point: only the occupied slots reach Python."""
+    keys, counts = tables["keys"].cpu().numpy().view(np.uint64), tables["counts"].cpu().numpy()
+    out = []
+    for k in range(keys.shape[0]):
+        at = np.flatnonzero(keys[k] != NS.EMPTY)
+        out.append({H.signal_of_key(key): int(n) for key, n in zip(keys[k][at].tolist(), counts[k][at].tolist())})
+    return out
+
+
+# ---- the host path ----
+
+def _sweep_host(sequence, labels, num_mocks, num_edmans, points, n, seed, first_molecule, stride, fit, max_possible, allow_multidrop,
+                max_deviation, quench_factors, fixed):
+    """The sweep through the host twins, a point at a time: simulation_records(host=True), the restated fit of
+    simulate_peptide.host_fit, the twin's tally."""
+    from . import _host_lognormal
+    base, values, keys = _point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points, fixed)
+    sims, totals, nones = {}, {}, {}
+    if fit:
+        means = _tracks.log_fluor_means(fixed['beta'], quench_factors, max_possible)
+    for k, key in enumerate(keys):
+        ep = {x: v for x, v in fixed.items() if x != 'b'}
+        ep.update(zip(("p", "per_cycle_b", "u", "s", "s2"), values[k].tolist()))
+        rec = PS.simulation_records(sequence, labels, num_mocks, num_edmans, n, seed, first_molecule + k * stride, host=True, **ep)
+        kept = np.flatnonzero(rec["category"] != 0)
+        rows = rec["counts"][kept]
+        (mol,), _, unkeyed = H.tally_rows(rows, np.zeros(len(rows), np.int32), None, 1)
+        signals, total, none_count = ({}, len(kept), 0) if fit else (None, len(kept), None)
+        if fit and len(kept):
+            fits = [_host_lognormal.intensities_to_signal(rec["intensity"][i].tolist(), fixed['beta_sigma'], max_possible, allow_multidrop,
+                                                          max_deviation, tuple(c != 0 for c in rec["counts"][i].tolist()), means)
+                    for i in kept.tolist()]
+            best = [f[2] for f in fits if f[2] is not None]
+            none_count = len(fits) - len(best)
+            (signals,), _, more = H.tally_rows(np.array(best, np.uint8).reshape(len(best), rows.shape[1]),
+                                               np.zeros(len(best), np.int32), None, 1)
+            unkeyed[0] += more[0]
+            signals = {H.signal_of_key(x): c for x, c in signals.items()}
+        if unkeyed[0]:
+            raise NotImplementedError("point %d has signals with more than %d drops, or that start above 15 dyes" % (k, H.MAX_DROPS))
+        sims[key] = (signals, {H.signal_of_key(x): c for x, c in mol.items()})
+        totals[key], nones[key] = total, none_count
+    return {"points": keys, "all_simulations": sims, "total_count": totals, "none_count": nones}
+
+
+def sweep_records(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=0, first_molecule=0, molecule_stride=0,
+                  fit=True, max_possible=5, allow_multidrop=True, max_deviation=3, quench_factors=None, solver=None, table_slots=1024,
+                  chunk_rows=1 << 22, device=None, host=False, **fixed_parameters):
+    """sweep_device's result as the reference's dicts: `all_simulations` {point: (signals, molecular_signals)} as
+    jupyter_development.py collects the pickles of simulate_peptide.py, `total_count` and `none_count` {point: n}, and `points`
+    in grid order.  host=True: the same through the host twins, without a GPU."""
+    if host:
+        n, stride, _, _ = _check_sweep_shape(num_simulations, molecule_stride, table_slots, chunk_rows)
+        return _sweep_host(sequence, labels, num_mocks, num_edmans, points, n, seed, first_molecule, stride, fit, max_possible,
+                           allow_multidrop, max_deviation, quench_factors, fixed_parameters)
+    sweep = sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed, first_molecule, molecule_stride, fit,
+                         max_possible, allow_multidrop, max_deviation, quench_factors, solver, table_slots, chunk_rows, device,
+                         **fixed_parameters)
+    return records_of_sweep(sweep)
+
+
+def records_of_sweep(sweep):
+    """sweep_records' dict of sweep_device's."""
+    keys = sweep["points"]
+    mol = _decode_tables(sweep["molecular"])
+    sig = _decode_tables(sweep["signals"]) if sweep["signals"] is not None else [None] * len(keys)
+    total = sweep["total_count"].cpu().tolist()
+    none = sweep["none_count"].cpu().tolist() if sweep["none_count"] is not None else [None] * len(keys)
+    return {"points": keys, "all_simulations": {key: (sig[k], mol[k]) for k, key in enumerate(keys)},
+            "total_count": dict(zip(keys, total)), "none_count": dict(zip(keys, none))}
+
+
+# ---- scoring ----
+
+def _score_options(kw):
+    unknown = set(kw) - set(_SCORE_KW) - {"matching_p", "print_included_signals", "euclidean_weights"}
+    if unknown:
+        raise TypeError("unexpected keyword %r" % sorted(unknown)[0])
+    return {k: v for k, v in kw.items() if k in _SCORE_KW}
+
+
+def _scores_on_device(table, d_fit, d_fit_total, metric, normalization, small_count_cutoff, contributions):
+    torch = _engine._torch()
+    dev = d_fit.device
+    S, P = (int(x) for x in d_fit.shape)
+    prm = NS.FsqScoreParams()
+    prm.n_observed, prm.metric, prm.normalization = table["n_observed"], H.check_metric(metric), normalization
+    prm.has_cutoff, prm.small_count_cutoff = (0, 0.0) if small_count_cutoff is None else (1, float(small_count_cutoff))
+    d = {k: torch.from_numpy(table[k]).to(dev) for k in ("observed", "in_observed", "admitted", "heatmap")}
+    out = {"score": torch.empty(P, dtype=torch.float64, device=dev), "factor": torch.empty(P, dtype=torch.float64, device=dev),
+           "status": torch.empty(P, dtype=torch.int32, device=dev),
+           "contributions": torch.empty((S, P), dtype=torch.float64, device=dev) if contributions else None}
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None       # noqa: E731
+    _engine.launch(NS.lib().fsq_signal_scores, "fsq_signal_scores", dev, ptr(d["observed"]), ptr(d["in_observed"]), ptr(d["admitted"]),
+                   ptr(d["heatmap"]), ptr(d_fit), d_fit_total.data_ptr(), S, P, ctypes.byref(prm), out["score"].data_ptr(),
+                   out["factor"].data_ptr(), out["status"].data_ptr(), ptr(out["contributions"]))
+    out["signals"] = table["signals"]
+    return out
+
+
+def score_device(observed_signals, sweep, metric='naive', normalize_counts=False, heatmap_normalize_counts=False,
+                 small_count_cutoff=None, contributions=True, molecular=False, device=None, **kw):
+    """signal_correlation of observed_signals against every point of a sweep, on the device: a dict of CUDA tensors score and
+    factor float64 [P], status int32 [P] (0 ok, 1 nothing pairs, 2 ZeroDivisionError, 3 ValueError), contributions float64
+    [S, P] (NaN: none) or None, and `signals`, the S signals in the order of the sums.  `sweep` is sweep_device's dict (its
+    tables are read where they are) or sweep_records' (its dicts are uploaded as a count matrix); molecular=True scores the
+    molecular signals instead of the fitted ones.  The keywords are signal_correlation's."""
+    torch = _engine._torch()
+    opts, norm = _score_options(kw), H.normalization_of(normalize_counts, heatmap_normalize_counts)
+    H.check_metric(metric)
+    if "all_simulations" in sweep:
+        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
+        signals = H.ordered_signals(set(observed_signals).union(*dicts))
+        fit, fit_total = H.fit_matrix(signals, dicts)
+        dev = torch.device(device or "cuda")
+        d_fit, d_total = torch.from_numpy(fit).to(dev), torch.from_numpy(fit_total).to(dev)
+    else:
+        tables = sweep["molecular" if molecular else "signals"]
+        if tables is None:
+            raise ValueError("the sweep was run with fit=False: pass molecular=True")
+        occupied = torch.unique(tables["keys"][tables["keys"] != NS.EMPTY]).cpu().tolist()
+        signals = H.ordered_signals(set(observed_signals) | {H.signal_of_key(k) for k in occupied})
+        wanted = [H.key_of_signal(s) for s in signals]
+        d_wanted = torch.from_numpy(np.array([NS.NEVER if k is None else k for k in wanted], np.uint64).view(np.int64)).to(tables["keys"].device)
+        d_fit, d_total = lookup_device(tables, d_wanted), tables["counts"].sum(dim=1)
+        if int(d_total.max()) > NS.MAX_COUNT:
+            raise NotImplementedError("counts beyond 2^31 - 1")
+    table = H.key_table(observed_signals, signals, **opts)
+    return _scores_on_device(table, d_fit, d_total, metric, norm, small_count_cutoff, contributions)
+
+
+def score_records(observed_signals, sweep, metric='naive', normalize_counts=False, heatmap_normalize_counts=False,
+                  small_count_cutoff=None, contributions=True, molecular=False, host=False, on_error='raise', device=None, **kw):
+    """{point: (result, (normalization_factor, contributions))} as match_diagnostic's all_correlations (:921-936).  A point at
+    which the reference raises (a heatmap total of zero, a zero variance) raises here as well, or with on_error='none' gets the
+    result None.  host=True: the NumPy twin (sweep_records' dict is then needed)."""
+    if on_error not in ('raise', 'none'):
+        raise ValueError("on_error must be 'raise' or 'none'")
+    if host:
+        opts, norm = _score_options(kw), H.normalization_of(normalize_counts, heatmap_normalize_counts)
+        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
+        signals = H.ordered_signals(set(observed_signals).union(*dicts))
+        fit, fit_total = H.fit_matrix(signals, dicts)
+        score, factor, status, contrib = H.scores(H.key_table(observed_signals, signals, **opts), fit, fit_total, metric, norm,
+                                                  small_count_cutoff, contributions)
+    else:
+        out = score_device(observed_signals, sweep, metric, normalize_counts, heatmap_normalize_counts, small_count_cutoff,
+                           contributions, molecular, device, **kw)
+        signals = out["signals"]
+        score, factor, status = (out[k].cpu().numpy() for k in ("score", "factor", "status"))
+        contrib = out["contributions"].cpu().numpy() if contributions else None
+    results = {}
+    for k, key in enumerate(sweep["points"]):
+        if on_error == 'none' and status[k] in (H.SCORE_DIVZERO, H.SCORE_DOMAIN):
+            results[key] = (None, (None, {}))
+        else:
+            results[key] = H.result_of(signals, score, factor, status, contrib, k)
+    return results
+
+
+def best_point(scores, reverse_order=False):
+    """(point, result, normalization_factor, contributions) of the best point of score_records' dict, as match_diagnostic takes
+    it (:938-948): the smallest result, or with reverse_order the largest.  Ties go to the first point in grid order; a point
+    whose result is None is never chosen."""
+    best = None
+    for key, (result, (factor, contrib)) in scores.items():
+        if result is None:
+            continue
+        if best is None or (result > best[1] if reverse_order else result < best[1]):
+            best = (key, result, factor, contrib)
+    if best is None:
+        raise ValueError("no point has a result")
+    return best
+
+
+def signal_correlation(observed_signals, fit_signals, heatmap_only=True, zero_only=True, metric='naive', normalize_counts=False,
+                       matching_p=0.10, exclude_signals=None, print_included_signals=False, select_signals=None,
+                       heatmap_normalize_counts=False, allow_multidrop=False, small_count_cutoff=None, euclidean_weights=None,
+                       host=False, device=None):
+    """jupyter_development.signal_correlation (:279-578) for one pair of dicts: (result, (normalization_factor,
+    contributions)).  A fit signal counts as present when its count is positive.  host=True runs the NumPy twin without a GPU."""
+    sweep = {"points": [0], "all_simulations": {0: (fit_signals, None)}}
+    return score_records(observed_signals, sweep, metric, normalize_counts, heatmap_normalize_counts, small_count_cutoff, True, False,
+                         host, 'raise', device, heatmap_only=heatmap_only, zero_only=zero_only, exclude_signals=exclude_signals,
+                         select_signals=select_signals, allow_multidrop=allow_multidrop)[0]
