@@ -164,8 +164,8 @@ def scores(table, fit, fit_total, metric, normalization=0, small_count_cutoff=No
     m = check_metric(metric)
     obs, in_obs, adm, heat = (table[k].tolist() for k in ("observed", "in_observed", "admitted", "heatmap"))
     S, n_obs = len(obs), table["n_observed"]
-    fit = np.asarray(fit, dtype=np.int64).reshape(S, -1)
-    P = fit.shape[1]
+    P = len(fit_total)
+    fit = np.asarray(fit, dtype=np.int64).reshape(S, P)                 # (S = 0: no keys, P points all the same)
     score, factor = np.full(P, np.nan), np.full(P, np.nan)
     status = np.zeros(P, np.int32)
     contrib = np.full((S, P), np.nan) if contributions else None

@@ -414,7 +414,8 @@ extern "C" int fsq_signal_scores(const int64_t* d_observed, const uint8_t* d_in_
                                  double* d_contrib, void* stream)
 {
     if (!prm || n_keys < 0 || n_points < 1) return FSQ_EINVAL;
-    if (prm->metric < 0 || prm->metric >= FSQ_SCORE_N_METRICS || (prm->normalization & ~3) || prm->n_observed < 0) return FSQ_EINVAL;
+    if (prm->metric < 0 || prm->metric >= FSQ_SCORE_N_METRICS || (prm->normalization & ~3)) return FSQ_EINVAL;
+    if (prm->n_observed < 0 || prm->n_observed > 2147483647ll) return FSQ_EINVAL;       // (oi * (n_observed - oi) stays within 64 bits)
     if (prm->has_cutoff && prm->small_count_cutoff != prm->small_count_cutoff) return FSQ_EINVAL;
     if (!d_fit_total || !d_score || !d_factor || !d_status) return FSQ_EINVAL;
     if (n_keys > 0 && (!d_observed || !d_in_observed || !d_admitted || !d_heatmap || !d_fit)) return FSQ_EINVAL;

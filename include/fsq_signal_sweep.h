@@ -95,7 +95,8 @@ int fsq_signal_lookup(const uint64_t* d_keys, const int64_t* d_counts, int32_t n
 #define FSQ_SCORE_DOMAIN 3                  /* the reference raises ValueError: a maximum of nothing, a root of a negative */
 
 typedef struct {
-    int64_t n_observed;                     /* the std metrics' n: the observed counts that pass zero_only and allow_multidrop */
+    int64_t n_observed;                     /* the std metrics' n: the observed counts that pass zero_only and allow_multidrop.
+                                             * 0 .. 2^31 - 1, as every count: beyond it fsq_signal_scores returns FSQ_EINVAL. */
     double small_count_cutoff;              /* read when has_cutoff != 0 */
     int32_t has_cutoff;
     int32_t normalization;                  /* FSQ_SCORE_NORMALIZE_COUNTS | FSQ_SCORE_HEATMAP_NORMALIZE_COUNTS */
