@@ -10,8 +10,9 @@
 //                         fdjac2 + qrfac + Q^T f + gradient test            mpfit.py:1064-1160
 //   kB  "step round"      one lane per fit, R in registers: lmpar, bounded step, trial evaluation,
 //                         trust-region update, convergence tests             mpfit.py:1163-1335
-//                         (ONE launch per round over five lists: fresh records binned by how many Newton iterations
-//                         lmpar needed for that fit last time, and fits parked in the middle of lmpar - see CNT_* below)
+//                         (ONE launch per round over six lists: records binned four ways by how many Newton iterations
+//                         lmpar needed for that fit last time, and fits parked in the middle of lmpar in two more - see
+//                         CNT_* below and fsq_kb_tilemap.h)
 // Each kernel takes one queue entry group per block (16 fits in kA, 64 in kB) and appends every fit to the
 // queue of the kernel it needs next (accepted step -> kA, rejected step -> kB again, terminated -> done), so
 // every wave of every launch is full, whatever the iteration counts are.  Kernel boundaries give the
@@ -31,6 +32,7 @@
 #include "fsq_common.h"
 #include "fsq_lm_quad.h"
 #include "fsq_evalguard.h"
+#include "fsq_kb_tilemap.h"
 
 namespace {
 
@@ -67,13 +69,19 @@ __device__ unsigned long long g_rphase[32];
 // Indexed by candidate: a compact 64-byte copy of the 25 ROI pixels (kinit), the model's 25 exponentials E at the current
 // point (written on acceptance, read by kA, which rebuilds fvec = data - (x0 + x1 E) from them), the final result, the ROI
 // statistics.
-// Counters of one ping/pong set of queues (8 ints): fits waiting in queue A, in the two lists of queue B and the two of queue C.
-// Queues B and C each hold TWO lists in one array, one growing from position 0 upwards and one from cap - 1 downwards:
-//   B lo / hi   input of the step round, binned by the number of Newton iterations lmpar took for this fit LAST time
-//               (<= 1 / more: the count is sticky per fit, oracle statistics in DESIGN.md) - a wave's lanes then mostly finish
-//               lmpar together instead of all waiting for the slowest
-//   C 1 / 3     fits parked in the middle of lmpar after 1 resp. 3 iterations; they are picked up by the NEXT round's launch
-enum { CNT_A = 0, CNT_BLO = 1, CNT_BHI = 2, CNT_C1 = 3, CNT_C3 = 4, CNT_SET = 8 };
+// Counters of one ping/pong set of queues: fits waiting in queue A, in the four lists of queue B and the two of queue C.
+// Every counter has a 128-byte line of its own (CNT_LINE ints apart): a line takes 88 wave-aggregated atomics per microsecond
+// whatever the number of counters in it, and the lines add up - with the seven tails in one line the Jacobian
+// round's up to four reservations per wave would saturate it.
+// An array of queue B / C holds TWO lists, one growing from position 0 upwards and one from cap - 1 downwards; queue B has two
+// such arrays back to back (the second starts B_LEN * cap doubles behind the first), queue C one (fsq_kb_tilemap.h):
+//   B 0 / 1 / 3 / 10   input of the step round, binned by the number of Newton iterations lmpar took for this fit LAST time
+//               (<= 0 / 1 / 2..4 / more: the count is sticky per fit, oracle statistics in DESIGN.md) - a wave's lanes then
+//               finish lmpar together instead of all waiting for the slowest
+//   C 1 / 3     fits parked in the middle of lmpar before resp. after their third iteration; the NEXT round's launch picks them up
+enum { CNT_LINE = 32, CNT_A = 0, CNT_B0 = CNT_LINE, CNT_C1 = CNT_B0 + KB_C1 * CNT_LINE, CNT_C3 = CNT_B0 + KB_C3 * CNT_LINE,
+       CNT_KINDS = 1 + KB_LISTS, CNT_SET = 8 * CNT_LINE };
+__host__ __device__ inline int cnt_of_list(int list) { return CNT_B0 + list * CNT_LINE; }     // list: KB_B0 .. KB_C3
 enum { Q_EPS = Q_WA3 };           // kA, during qrfac: relative error bounds of the tracked column norms (by logical position)
 enum { A_IDX = 0, A_X = 1, A_DIAG = 8, A_LLIM1 = 15, A_FNORM = 16, A_PAR = 17, A_DELTA = 18, A_XNORM = 19, A_ITER = 20,
        A_HDR = 21 /* the part every kind of record starts with */, A_E = 21 /* queue A only: the model's 25 exponentials E at x */, A_LEN = 46,
@@ -113,8 +121,8 @@ struct Ctx {
 // queues from upper bounds it keeps itself (FsqFitQueue::alive), and if one of those bounds were ever wrong the write would
 // land outside the workspace - a memory fault at best, silent damage at worst.  A position out of range is recorded (the
 // largest code wins; FsqFitQueue::look turns it into FSQ_EINTERNAL) and replaced by position 0, which is inside.
-enum { G_KINIT_POS = 1, G_KINIT_SLOT = 2, G_KA_BLO = 3, G_KA_BHI = 4, G_KA_OVERLAP = 5, G_KA_SLOW = 6, G_KB_C1 = 7, G_KB_C3 = 8, G_KB_A = 9,
-       G_KB_BLO = 10, G_KB_BHI = 11 };
+enum { G_KINIT_POS = 1, G_KINIT_SLOT = 2, G_KA_B = 3, G_KA_OVERLAP = 5, G_KA_SLOW = 6, G_KB_C1 = 7, G_KB_C3 = 8, G_KB_A = 9,
+       G_KB_B = 10 };
 FSQ_DEV long long fsq_guard(const Ctx& c, long long v, long long limit, int code)
 {
     if ((unsigned long long)v < (unsigned long long)limit) return v;
@@ -134,6 +142,27 @@ FSQ_DEV int wave_reserve(int* counter, bool want)
     if (lane == leader) base = atomicAdd(counter, __popcll(m));
     base = __shfl(base, leader);
     return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// The same for lanes that append to DIFFERENT lists, list `list` (0 .. 3) of lane `want` having its counter at
+// counters[list * CNT_LINE]: the leaders of the lists are different lanes, so the up to four atomics leave in ONE instruction
+// and the wave waits for one round trip, not four.  *other receives the wave's view of the tail of the list that shares the
+// lane's array (list ^ 1): its reservation's end if the wave appended there, 0 if not.
+FSQ_DEV int wave_reserve4(int* counters, bool want, int list, int* other)
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long m[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) m[l] = __ballot(want && list == l);
+    const unsigned long long mine = list == 0 ? m[0] : list == 1 ? m[1] : list == 2 ? m[2] : m[3];
+    const unsigned long long pair = list == 0 ? m[1] : list == 1 ? m[0] : list == 2 ? m[3] : m[2];
+    const int leader = want ? __ffsll((long long)mine) - 1 : lane;
+    int base = 0;
+    if (want && lane == leader) base = atomicAdd(counters + list * CNT_LINE, __popcll(mine));
+    const int pair_base = __shfl(base, pair ? __ffsll((long long)pair) - 1 : lane);       // (all lanes shuffle: no divergence here)
+    base = __shfl(base, leader);
+    *other = pair ? pair_base + __popcll(pair) : 0;
+    return want ? base + __popcll(mine & ((1ull << lane) - 1ull)) : 0;
 }
 
 // ... and the position checked against the list's capacity - for the lanes that will WRITE there only: a lane that does not
@@ -421,7 +450,7 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
     if (c.wave_prio) __builtin_amdgcn_s_setprio(3);
     const int cntA = FAST ? *cntA_p : *slow_cnt;
     if (!FAST && blockIdx.x == 0 && threadIdx.x == 0 && cntA > 0) atomicAdd(c.slow_total, cntA);
-    if (FAST && blockIdx.x == 0 && threadIdx.x < CNT_SET) next_counters[threadIdx.x] = 0;
+    if (FAST && blockIdx.x == 0 && threadIdx.x < CNT_KINDS) next_counters[threadIdx.x * CNT_LINE] = 0;
     double col[NC][FSQ_NPIX];
     RPH_DECL
     const long long cap = c.cap;
@@ -441,24 +470,17 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
         unpack2(__shfl(rec[A_IDX / L], gbase + A_IDX % L), &tag, &hist);
         unpack2(__shfl(rec[A_ITER / L], gbase + A_ITER % L), &niter, &nfev);
         // this fit's queue-B slot (see above), in the list its lmpar history selects
-        const bool b_hi = hist > 1;
-        const int at_lo = wave_reserve(cnt_cur + CNT_BLO, active && cl == 0 && !b_hi);
-        const int at_hi = wave_reserve(cnt_cur + CNT_BHI, active && cl == 0 && b_hi);
-#ifdef FSQ_EXPERIMENT_EXTRA_ATOMICS_KA   // sensitivity of the round to the queue-tail atomics: N more per wave on the same cache line
-        {
-            int sink = 0;
-            for (int x = 0; x < FSQ_EXPERIMENT_EXTRA_ATOMICS_KA; x++) sink += wave_reserve(cnt_cur + 5 + (x & 1), active && cl == 0);
-            if (sink == 0x7fffffff) atomicMax(c.err, 99);
-        }
-#endif
+        const int blist = kb_list_of_history(hist);        // KB_B0 .. KB_B10
+        int at_pair;
+        const int at_mine = wave_reserve4(cnt_cur + CNT_B0, active && cl == 0, blist, &at_pair);
         if (active && cl == 0) {      // (two lists in one array, growing towards each other)
-            if (!b_hi) fsq_guard(c, at_lo, cap, G_KA_BLO); else fsq_guard(c, at_hi, cap, G_KA_BHI);
-            if ((long long)at_lo + (long long)at_hi + 2 > cap && (at_lo > 0 || at_hi > 0)) {
-                const int nlo = b_hi ? cnt_cur[CNT_BLO] : at_lo + 1, nhi = b_hi ? at_hi + 1 : cnt_cur[CNT_BHI];
-                if ((long long)nlo + nhi > cap) atomicMax(c.err, (int)G_KA_OVERLAP);
+            if ((long long)at_mine + (long long)at_pair + 2 > cap && (at_mine > 0 || at_pair > 0)) {
+                if ((long long)at_mine + 1 + cnt_cur[cnt_of_list(blist ^ 1)] > cap) atomicMax(c.err, (int)G_KA_OVERLAP);
             }
         }
-        const long long at = __shfl((active && cl == 0) ? (int)fsq_guard(c, b_hi ? (long long)(cap - 1) - at_hi : (long long)at_lo, cap, b_hi ? G_KA_BHI : G_KA_BLO) : 0, gbase);
+        // (position in the list -> position in the array -> offset from QB in doubles: the second array lies behind the first)
+        const long long at = __shfl((active && cl == 0) ? (int)kb_list_pos(blist, fsq_guard(c, at_mine, cap, G_KA_B), cap) : 0, gbase)
+                             + (long long)kb_list_array(blist) * (B_LEN * cap);
         const int idx = tag_slot(c, tag);
         const bool fresh = active && (nfev == 0);
         double llim1 = 0., fnorm = 0., xnorm = 0., delta = 0., par_in = 0.;
@@ -1088,18 +1110,18 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
 // kB: step round.  One lane per fit, one 64-fit tile per block.
 // lmpar's Newton iteration on par takes 0 or 1 iterations for half of the fits, 3 for a fifth and all 10 for a quarter of them
 // - and whatever a fit needed last time it most likely needs again (0 -> 0: 90 %, 1 -> 1: 86 %, 3 -> 3: 75 %, 10 -> 10: 82 %).
-// A wave waits for its slowest lane, so the fits are kept apart by that history: queue B holds two lists (last count <= 1 / more),
-// whose tiles stop lmpar after 1 resp. 3 iterations and PARK the lanes that are not done (their R / sdiag / par state as it
-// stands) in queue C, again in two lists (parked after 1 / after 3 iterations); the next round's launch picks those up and
-// runs them to 3 resp. to the end.  One launch per round works off all four lists.
+// A wave waits for its slowest lane, so the fits are kept apart by that history: queue B holds four lists (last count <= 0 / 1 /
+// 2..4 / more), whose tiles stop lmpar after 0 / 3 / 3 / all 10 iterations and PARK the lanes that are not done (their R / sdiag /
+// par state as it stands) in queue C, in two lists (parked before / after the third iteration); the next round's launch picks
+// those up and runs them to 3 resp. to the end.  One launch per round works off all six lists.  (A B1 tile leaves the loop as
+// soon as all its lanes are done - after one pass for most - so its limit of 3 costs passes only where a lane needs them and
+// saves that lane the park and the resumed tile: measured 1.7 ms per step better than a limit of 1, profiles/r07_summary.md.)
 #ifndef FSQ_KA_LANES_DEFAULT
 #define FSQ_KA_LANES_DEFAULT 4
 #endif
-#ifndef FSQ_LMPAR_FIRST
-#define FSQ_LMPAR_FIRST 5
-#endif
-#ifndef FSQ_LMPAR_LO
-#define FSQ_LMPAR_LO 1
+// the staged limits of the six kinds of tiles, in the order of fsq_kb_tilemap.h (B0, B1, B3, B10, C1, C3)
+#ifndef FSQ_LMPAR_LIMITS
+#define FSQ_LMPAR_LIMITS {0, 3, 3, 10, 3, 10}
 #endif
 #ifndef FSQ_KB_WAVES
 #define FSQ_KB_WAVES 2
@@ -1144,7 +1166,7 @@ FSQ_DEV bool kb_trial_gauss(const double* p, double* myscr)
 
 FSQ_DEV double kb_late_load(const NtRef r) { asm volatile("" ::: "memory"); return (double)r; }
 
-struct KbLimits { int lim[4]; };        // lmpar iteration limits of the four kinds of tiles: B lo, B hi, C 1, C 3
+struct KbLimits { int lim[KB_LISTS]; }; // lmpar iteration limits of the six kinds of tiles, by list (KB_B0 .. KB_C3)
 template <bool ALIASED, bool P32 = false>
 __global__ void __launch_bounds__(64, FSQ_KB_WAVES) kB_step(Ctx c, const double* __restrict__ QB, const double* __restrict__ QC,
                                                   const int* __restrict__ cnt_cur,
@@ -1158,22 +1180,20 @@ __global__ void __launch_bounds__(64, FSQ_KB_WAVES) kB_step(Ctx c, const double*
     double* myscr = scr + lane;
     RPH_DECL
     {
-        // One launch works off all four input lists, one 64-fit tile per block, the long-running kinds first: fits parked after
-        // 3 iterations (they run up to 7 more), B hi (3 iterations, then parked), fits parked after 1 iteration, B lo.
-        int b = blockIdx.x, seg, cnt;
-        const int n_lo = cnt_cur[CNT_BLO], n_hi = cnt_cur[CNT_BHI], n_c1 = cnt_cur[CNT_C1], n_c3 = cnt_cur[CNT_C3];
-        if (b < (n_c3 + 63) / 64) { seg = 3; cnt = n_c3; }
-        else if ((b -= (n_c3 + 63) / 64) < (n_hi + 63) / 64) { seg = 1; cnt = n_hi; }
-        else if ((b -= (n_hi + 63) / 64) < (n_c1 + 63) / 64) { seg = 2; cnt = n_c1; }
-        else if ((b -= (n_c1 + 63) / 64) < (n_lo + 63) / 64) { seg = 0; cnt = n_lo; }
-        else return;
-        const bool resume = seg >= 2;               // (wave-uniform)
+        // One launch works off all six input lists, one 64-fit tile per block, the long-running kinds first (fsq_kb_tilemap.h)
+        int n_in[KB_LISTS];
+#pragma unroll
+        for (int l = 0; l < KB_LISTS; l++) n_in[l] = cnt_cur[cnt_of_list(l)];
+        const KbTile tile = kb_tile_of_block(blockIdx.x, n_in);
+        if (tile.list < 0) return;
+        const int seg = tile.list, cnt = tile.count;
+        const bool resume = seg >= KB_C1;           // (wave-uniform)
         const int lm_limit = lims.lim[seg];
-        const int base = b * 64;
+        const int base = tile.tile * 64;
         RPH_MARK(0)
         bool live = (base + lane) < cnt;
         const int p_in = live ? (base + lane) : base;
-        const NtQ qb = ntq((resume ? QC : QB) + ((seg & 1) ? cap - 1 - p_in : p_in));
+        const NtQ qb = ntq((resume ? QC : QB + (long long)kb_list_array(seg) * (B_LEN * cap)) + kb_list_pos(seg, p_in, cap));
         // DEAD slots (tag -1: reserved early by the Jacobian round and not needed, only their tag is written) and the idle lanes
         // of a list's last tile hold no fit: they do not read the record at all and work on a fixed, valid stand-in instead
         // (an identity R, a zero right-hand side, the start point of a fit), so that no address, table index or LDS offset of
@@ -1239,7 +1259,7 @@ __global__ void __launch_bounds__(64, FSQ_KB_WAVES) kB_step(Ctx c, const double*
             {
                 // unfinished: park the fit (R / sdiag / par state as they stand) for the next round's launch
                 const bool park = live && !st.done;
-                const bool to_c1 = (st.iter < lims.lim[2]);            // (C 1 tiles run to lim[2], C 3 tiles to the end: always progress)
+                const bool to_c1 = (st.iter < lims.lim[KB_C1]);        // (C 1 tiles run to lim[KB_C1], C 3 tiles to the end: always progress)
                 const int at1 = (int)wave_reserve_checked(c, cnt_next + CNT_C1, park && to_c1, cap, G_KB_C1);
                 const int at3 = (int)wave_reserve_checked(c, cnt_next + CNT_C3, park && !to_c1, cap, G_KB_C3);
                 if (park) {
@@ -1443,19 +1463,13 @@ __global__ void __launch_bounds__(64, FSQ_KB_WAVES) kB_step(Ctx c, const double*
         {
             // accepted -> a new Jacobian (queue A); rejected -> another pass with the same, mutated R (queue B)
             const bool toA = live && status == 0 && accepted, toB = live && status == 0 && !accepted;
-            const bool hi = lm_hist > 1;
-#ifdef FSQ_EXPERIMENT_EXTRA_ATOMICS_KB
-            {
-                int sink = 0;
-                for (int x = 0; x < FSQ_EXPERIMENT_EXTRA_ATOMICS_KB; x++) sink += wave_reserve(cnt_next + 5 + (x & 1), live);
-                if (sink == 0x7fffffff) atomicMax(c.err, 99);
-            }
-#endif
+            const int blist = kb_list_of_history(lm_hist);      // a rejected step: the list of the fit's NEW history
             const int atA = (int)wave_reserve_checked(c, cnt_next + CNT_A, toA, cap, G_KB_A);
-            const int atBl = (int)wave_reserve_checked(c, cnt_next + CNT_BLO, toB && !hi, cap, G_KB_BLO);
-            const int atBh = (int)wave_reserve_checked(c, cnt_next + CNT_BHI, toB && hi, cap, G_KB_BHI);
+            int atB_pair;       // (unused: live fits number at most cap, and each is in one list of set nxt)
+            const int atB = wave_reserve4(cnt_next + CNT_B0, toB, blist, &atB_pair);
             if (toA || toB) {
-                const NtQ qn = ntq(toA ? (QA_next + atA) : (QB_next + (hi ? cap - 1 - atBh : (long long)atBl)));
+                const NtQ qn = ntq(toA ? (QA_next + atA)
+                                       : (QB_next + (long long)kb_list_array(blist) * (B_LEN * cap) + kb_list_pos(blist, fsq_guard(c, atB, cap, G_KB_B), cap)));
                 qn[A_IDX * cap] = pack2(tag, lm_hist);
 #pragma unroll
                 for (int k = 0; k < FSQ_NP; k++) { qn[(A_X + k) * cap] = xq[k]; qn[(A_DIAG + k) * cap] = q.dg[k]; }
@@ -1711,7 +1725,8 @@ namespace {
 enum { CTL_SLOW_TOTAL = 2 * CNT_SET, CTL_SLOW_CNT = 2 * CNT_SET + 1, CTL_F32_NEXT = 2 * CNT_SET + 2, CTL_ERR = 2 * CNT_SET + 3, CTL_DONE = 2 * CNT_SET + 8, CTL_INTS = CTL_DONE + FSQ_MAX_TICKETS };
 
 struct RoundsCfg {
-    int lm_first = FSQ_LMPAR_FIRST, lm_lo = FSQ_LMPAR_LO, sync_mask = 3, force_slow_mod = 0, force_redo = 0, no_wave_prio = 0, trace = 0;
+    int lm_lim[KB_LISTS] = FSQ_LMPAR_LIMITS;           // staged rounds: where each kind of tile stops lmpar
+    int sync_mask = 3, force_slow_mod = 0, force_redo = 0, no_wave_prio = 0, trace = 0;
     int ka_lanes = FSQ_KA_LANES_DEFAULT;               // lanes per fit in the Jacobian round (4 or 8)
     int max_rounds = 0, ka_lds_pad = 0, kb_lds_pad = 0;      // (debug: extra dynamic LDS per block = fewer waves per CU)
     long long two_pass_min = 524288, hiprio_below = 200000;
@@ -1722,8 +1737,15 @@ RoundsCfg read_cfg()
     const char* e;
     if ((e = getenv("FSQ_DEBUG_FORCE_SLOW")) != nullptr) g.force_slow_mod = atoi(e);
     if ((e = getenv("FSQ_DEBUG_FORCE_NORM_RECOMPUTE")) != nullptr) g.force_redo = atoi(e) ? 1 : 0;
-    if ((e = getenv("FSQ_LMPAR_FIRST_ITERS")) != nullptr && atoi(e) >= 1 && atoi(e) <= 10) g.lm_first = atoi(e);
-    if ((e = getenv("FSQ_LMPAR_LO_ITERS")) != nullptr && atoi(e) >= 1 && atoi(e) <= 10) g.lm_lo = atoi(e);
+    // FSQ_LMPAR_FIRST_ITERS / FSQ_LMPAR_LO_ITERS are the names from the time of two B lists: where B3 tiles stop and parked fits
+    // resume to / where B1 tiles stop.  The C3 limit is not a knob: those tiles run to the end, which is what ends every fit.
+    if ((e = getenv("FSQ_LMPAR_FIRST_ITERS")) != nullptr && atoi(e) >= 1 && atoi(e) <= 10) g.lm_lim[KB_B3] = g.lm_lim[KB_C1] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_LO_ITERS")) != nullptr && atoi(e) >= 1 && atoi(e) <= 10) g.lm_lim[KB_B1] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_B0_ITERS")) != nullptr && atoi(e) >= 0 && atoi(e) <= 10) g.lm_lim[KB_B0] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_B1_ITERS")) != nullptr && atoi(e) >= 0 && atoi(e) <= 10) g.lm_lim[KB_B1] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_B3_ITERS")) != nullptr && atoi(e) >= 0 && atoi(e) <= 10) g.lm_lim[KB_B3] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_B10_ITERS")) != nullptr && atoi(e) >= 0 && atoi(e) <= 10) g.lm_lim[KB_B10] = atoi(e);
+    if ((e = getenv("FSQ_LMPAR_C1_ITERS")) != nullptr && atoi(e) >= 1 && atoi(e) <= 10) g.lm_lim[KB_C1] = atoi(e);
     if ((e = getenv("FSQ_TWO_PASS_MIN")) != nullptr) g.two_pass_min = atoll(e);
     if ((e = getenv("FSQ_HIPRIO_BELOW")) != nullptr) g.hiprio_below = atoll(e);
     if ((e = getenv("FSQ_SYNC_EVERY")) != nullptr && atoi(e) >= 1) g.sync_mask = atoi(e) - 1;     // power of two
@@ -1780,7 +1802,7 @@ size_t layout_bytes(size_t pool, size_t qcap)
     qcap = cap_round(qcap);
     size_t b = 4096;
     b += al256(pool * 128) + al256(pool * sizeof(FitOut)) + al256(pool * sizeof(FitStat));      // (ROI copies: room for 32-bit pixels)
-    b += 2 * al256(qcap * A_LEN * 8) + 2 * al256(qcap * B_LEN * 8) + 2 * al256(qcap * C_LEN * 8) + al256(qcap * A_LEN * 8);
+    b += 2 * al256(qcap * A_LEN * 8) + 2 * al256(2 * qcap * B_LEN * 8) + 2 * al256(qcap * C_LEN * 8) + al256(qcap * A_LEN * 8);
     return b;
 }
 }  // namespace
@@ -1821,8 +1843,8 @@ struct FsqFitQueue {
         c.stat = (FitStat*)(ws + o); o += al256(pool * sizeof(FitStat));
         QA[0] = (double*)(ws + o); o += al256(qcap * A_LEN * 8);
         QA[1] = (double*)(ws + o); o += al256(qcap * A_LEN * 8);
-        QB[0] = (double*)(ws + o); o += al256(qcap * B_LEN * 8);
-        QB[1] = (double*)(ws + o); o += al256(qcap * B_LEN * 8);
+        QB[0] = (double*)(ws + o); o += al256(2 * qcap * B_LEN * 8);      // (two arrays of two lists each, back to back)
+        QB[1] = (double*)(ws + o); o += al256(2 * qcap * B_LEN * 8);
         QC[0] = (double*)(ws + o); o += al256(qcap * C_LEN * 8);
         QC[1] = (double*)(ws + o); o += al256(qcap * C_LEN * 8);
         SQ = (double*)(ws + o); o += al256(qcap * A_LEN * 8);
@@ -1927,14 +1949,16 @@ struct FsqFitQueue {
             hipLaunchKernelGGL((kA_jacobian<true, 4>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
         else
             FSQ_HIP_CHECK(hipMemsetAsync(cset[nxt], 0, CNT_SET * sizeof(int), s));
-        // every fit in flight is in one of the four input lists of the step round by now (or terminated, or in the slow queue)
-        const long long gB = (alive + 63) / 64 + 4;
+        // every fit in flight is in one of the six input lists of the step round by now (or terminated, or in the slow queue);
+        // each list may end in a partial tile
+        const long long gB = kb_grid_for(alive);
         {
             // With few fits left a round is pure launch + wave latency: lmpar then runs to the end wherever a fit is met
             // (nothing is parked, no fit waits for the next round).
-            const bool staged = alive > cfg.two_pass_min && cfg.lm_first < 10;
+            const bool staged = alive > cfg.two_pass_min;
             KbLimits lims;
-            lims.lim[0] = staged ? std::min(cfg.lm_lo, cfg.lm_first) : 10; lims.lim[1] = staged ? cfg.lm_first : 10; lims.lim[2] = staged ? cfg.lm_first : 10; lims.lim[3] = 10;
+            for (int l = 0; l < KB_LISTS; l++) lims.lim[l] = staged ? cfg.lm_lim[l] : 10;
+            lims.lim[KB_C3] = 10;           // (whatever was parked late runs to the end: every fit makes progress)
             if (c.pix32 && ref) hipLaunchKernelGGL((kB_step<true, true>), dim3((unsigned)gB), dim3(64), 0, s, c, QB[cur], QC[cur], cset[cur], QA[nxt], QB[nxt], QC[nxt], cset[nxt], lims);
             else if (c.pix32) hipLaunchKernelGGL((kB_step<false, true>), dim3((unsigned)gB), dim3(64), 0, s, c, QB[cur], QC[cur], cset[cur], QA[nxt], QB[nxt], QC[nxt], cset[nxt], lims);
             else if (ref) hipLaunchKernelGGL((kB_step<true>), dim3((unsigned)gB), dim3(64), cfg.kb_lds_pad, s, c, QB[cur], QC[cur], cset[cur], QA[nxt], QB[nxt], QC[nxt], cset[nxt], lims);
@@ -1954,14 +1978,25 @@ struct FsqFitQueue {
         const int* hc = h_ctl + CNT_SET * cur;
         boundA = hc[CNT_A];
         slow_pending = h_ctl[CTL_SLOW_CNT];
-        alive = boundA + hc[CNT_BLO] + hc[CNT_BHI] + hc[CNT_C1] + hc[CNT_C3] + slow_pending;
+        int nl[KB_LISTS];
+        for (int l = 0; l < KB_LISTS; l++) nl[l] = hc[cnt_of_list(l)];
+        alive = boundA + slow_pending;
+        for (int l = 0; l < KB_LISTS; l++) alive += nl[l];
         g_last_slow.store(h_ctl[CTL_SLOW_TOTAL]);
         if (h_ctl[CTL_ERR] != 0) {          // a kernel was about to write outside a queue / the pool (fsq_guard): an engine bug, say which
-            fprintf(stderr, "fsq: fit queue invariant %d broken (cap %lld, pool %lld, host bounds: A %lld alive %lld; counters A %d B %d+%d C %d+%d slow %d)\n",
-                    h_ctl[CTL_ERR], (long long)qcap, (long long)pool, boundA, alive, hc[CNT_A], hc[CNT_BLO], hc[CNT_BHI], hc[CNT_C1], hc[CNT_C3], h_ctl[CTL_SLOW_CNT]);
+            fprintf(stderr, "fsq: fit queue invariant %d broken (cap %lld, pool %lld, host bounds: A %lld alive %lld; counters A %d B %d+%d+%d+%d C %d+%d slow %d)\n",
+                    h_ctl[CTL_ERR], (long long)qcap, (long long)pool, boundA, alive, hc[CNT_A], nl[KB_B0], nl[KB_B1], nl[KB_B3], nl[KB_B10], nl[KB_C1], nl[KB_C3], h_ctl[CTL_SLOW_CNT]);
             return FSQ_EINTERNAL;
         }
-        if (cfg.trace) fprintf(stderr, "round %lld: A=%lld B=%d+%d C=%d+%d slow=%lld total_slow=%d\n", round - 1, boundA, hc[CNT_BLO], hc[CNT_BHI], hc[CNT_C1], hc[CNT_C3], slow_pending, h_ctl[CTL_SLOW_TOTAL]);
+        if (cfg.trace) {
+            // "left": what round - 1 appended to the set the next round reads (accepted steps in A, rejected ones in B, parked fits
+            // in C).  "stepped": the six lists as the step round of round - 1 consumed them - its set stays as it was until the
+            // next Jacobian round zeroes it, and only there do the B counts include what the Jacobian round appended.
+            const int* hp = h_ctl + CNT_SET * (cur ^ 1);
+            fprintf(stderr, "round %lld: left A=%lld B=%d+%d+%d+%d C=%d+%d slow=%lld total_slow=%d stepped B=%d+%d+%d+%d C=%d+%d\n", round - 1, boundA,
+                    nl[KB_B0], nl[KB_B1], nl[KB_B3], nl[KB_B10], nl[KB_C1], nl[KB_C3], slow_pending, h_ctl[CTL_SLOW_TOTAL],
+                    hp[cnt_of_list(KB_B0)], hp[cnt_of_list(KB_B1)], hp[cnt_of_list(KB_B3)], hp[cnt_of_list(KB_B10)], hp[cnt_of_list(KB_C1)], hp[cnt_of_list(KB_C3)]);
+        }
         int fin = 0;
         for (auto& t : b) {
             if (t.state != T_FLIGHT || h_ctl[CTL_DONE + t.a.ticket] < t.a.n) continue;
