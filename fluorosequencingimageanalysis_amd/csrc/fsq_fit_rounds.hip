@@ -431,7 +431,14 @@ FSQ_DEV double kag_dot25(const double* lds, int grp, int off)
 #else
 #define KA_HZ(code, cond) do { if (cond) hz = true; } while (0)
 #endif
-template <bool FAST, int L, bool P32 = false>
+// QRS: which of qrfac's seven steps are compiled with the step index as a constant (ka_step_of) - 0: none, two rolled loops;
+// 1: steps 3 .. 6; 2: all seven.  Production (FAST, four lanes) only: see the note at qr_step.
+#ifndef FSQ_KA_QR_STATIC
+#define FSQ_KA_QR_STATIC 1      // what the production launches use (tools/build_variant.sh <name> -DFSQ_KA_QR_STATIC=0|1|2 for A/B)
+#endif
+template <class T> struct ka_step_of { static constexpr int value = -1; };
+template <int J> struct ka_step_of<std::integral_constant<int, J>> { static constexpr int value = J; };
+template <bool FAST, int L, bool P32 = false, int QRS = 0>
 __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const double* __restrict__ QA, const int* __restrict__ cntA_p,
                                                                     double* __restrict__ QB, int* __restrict__ cnt_cur,
                                                                     double* __restrict__ SQ, int* __restrict__ slow_cnt,
@@ -443,6 +450,7 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
     constexpr int MREC = (A_HDR + L - 1) / L;   // record fields per lane (the header; E is fetched by pixel)
     constexpr bool EVAL_ALL = FAST && L == 4;   // (see KA_EVAL_LOOP)
     constexpr int EVAL_UNROLL = EVAL_ALL ? MPX : 1;
+    static_assert(QRS == 0 || (FAST && L == 4 && QRS <= 2), "static qrfac steps: the fast four-lane kernel only");
     static_assert(fsq_llim(4, 0.) == FSQ_EG_MIN_SIGMA && fsq_llim(5, 0.) == FSQ_EG_MIN_SIGMA, "fsq_evalguard.h: sigma floor != the fit's lower limit");
     __shared__ double lds[Q_KA_END * G];
     const int lane = threadIdx.x, grp = lane / L, cl = lane % L, gbase = lane - cl;
@@ -736,8 +744,21 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
             constexpr bool COMPACT = (L == 4);
             int my_slot = cl;
             unsigned lane_of = 0x32103210u;
-            auto qr_step = [&](const int j, auto cmp_tag) __attribute__((always_inline)) {
+            // Static steps (QRS): called with std::integral_constant<int, j> the step is a copy of its own in which len = 25 - j is
+            // a constant.  Its row loops stop at len, so the rows past the front - zeros the rolled form still multiplies, adds
+            // (+0 to a sum that starts at +0: the same bits) and stores - are not touched at all, the columns are not shifted
+            // (step j works on rows R0 .. R0 + len - 1 of the sets as they stood when the rolled steps ended), the norm sums
+            // lose their selects between the two groupings, and the last step keeps only what qtf[6] needs.  Every operation
+            // that remains is one the rolled form executes, on the same values in the same order.
+            constexpr int ROLLED = (QRS == 1) ? 3 : 0;      // shifts done by rolled steps before the first static one
+            auto qr_step = [&](auto jarg, auto cmp_tag) __attribute__((always_inline)) {
                 constexpr bool CMP = COMPACT && decltype(cmp_tag)::value;
+                constexpr int JS = ka_step_of<decltype(jarg)>::value;
+                constexpr bool ST = JS >= 0;
+                constexpr int R0 = ST ? JS - ROLLED : 0;            // first live row of the register sets
+                constexpr int LEN = ST ? FSQ_NPIX - JS : FSQ_NPIX;  // rows the loops run over
+                constexpr bool LAST = ST && JS == FSQ_NP - 1;       // only f is live, and only its first row is read again
+                const int j = jarg;
                 const int len = FSQ_NPIX - j;
                 if (REGPOS && !broken) {
                     // candidates: positions j .. 6 (norms are >= +0; a NaN among them sends the fit to the exact kernel, where
@@ -816,7 +837,7 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 bool brk = false;
                 auto publish = [&](const double* t) __attribute__((always_inline)) {
 #pragma unroll
-                    for (int i = 0; i < FSQ_NPIX; i++) { QL(Q_DATA, i) = t[i]; KA_ROWS(i); }
+                    for (int i = 0; i < LEN; i++) { QL(Q_DATA, i) = t[i]; KA_ROWS(i); }
                     if (!broken) {
                         // (step 0: the column is the one whose acnorm the same sum over the same 25 values gave just above)
                         double ajnorm;
@@ -831,26 +852,30 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     }
                 };
                 if (lane == owner) {
-                    if (CMP && j > 3) publish(col[0]);              // (after the move: no select between the register sets)
+                    if (!ST && CMP && j > 3) publish(col[0]);       // (after the move: no select between the register sets)
                     else {
-                        double t[FSQ_NPIX];
+                        double t[FSQ_NPIX];                         // (static step: the live rows, renamed; the sum stops at len)
 #pragma unroll
-                        for (int i = 0; i < FSQ_NPIX; i++) t[i] = (NC == 2 && (lj / L) != 0) ? col[NC - 1][i] : col[0][i];
+                        for (int i = 0; i < FSQ_NPIX; i++) {
+                            if (i >= LEN) t[i] = 0.0;
+                            else if (ST && CMP && JS > 3) t[i] = col[0][R0 + i];
+                            else t[i] = (NC == 2 && (lj / L) != 0) ? col[NC - 1][R0 + i] : col[0][R0 + i];
+                        }
                         publish(t);
                     }
                 }
                 WAVE_SYNC();
                 broken = broken || (__shfl((int)brk, owner) != 0);
                 if (CMP && j == 3) {
-                    // the move: lane cl takes the column of slot ns from the lane and the register set that hold it.  Rows 22 .. 24
-                    // are +0 in every column by now (three shifts), so they stay where they are.
+                    // the move: lane cl takes the column of slot ns from the lane and the register set that hold it.  Rolled steps:
+                    // rows 22 .. 24 are +0 in every column by now (three shifts), so they stay where they are.
                     const int ns = (cl < 3) ? nib_get(ipvt, 4 + cl) : 7;
                     const int src = gbase + (ns & 3);
                     const bool hi = (ns >> 2) != 0;
 #pragma unroll
-                    for (int i = 0; i < FSQ_NPIX - 3; i++) {
-                        const double a = __shfl(col[0][i], src), b = __shfl(col[NC - 1][i], src);
-                        col[0][i] = hi ? b : a;
+                    for (int i = 0; i < FSQ_NPIX - 3 && i < LEN; i++) {
+                        const double a = __shfl(col[0][R0 + i], src), b = __shfl(col[NC - 1][R0 + i], src);
+                        col[0][R0 + i] = hi ? b : a;
                     }
                     my_slot = ns;
                     lane_of = nib_set(nib_set(nib_set(lane_of, nib_get(ipvt, 4), 0), nib_get(ipvt, 5), 1), nib_get(ipvt, 6), 2);
@@ -862,10 +887,10 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     int er = 0;
                     if (FAST) KA_HZ(7, !fsq_divisor_in_range(ajn));
 #pragma unroll
-                    for (int m = 0; m < MPX; m++) {
+                    for (int m = 0; m < MPX && L * m < LEN; m++) {
                         const int i = cl + L * m;
-                        if (i < FSQ_NPIX) {
-                            const double raw = QL(Q_DATA, i);       // rows >= len are zeros
+                        if (i < LEN) {
+                            const double raw = QL(Q_DATA, i);       // rolled steps: rows >= len are zeros
                             if (FAST) { er = min(er, fsq_expo(raw)); KA_PIN(er); }
                             double q_ = fsq_div_sel<FAST>(raw, kn);
                             if (i == 0) q_ = q_ + 1;
@@ -893,19 +918,19 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     const bool todo = is_f ? true : (!broken && k > j);
                     if (todo && ajj0 != 0) {
                         double s = 0.0;
-                        // rows >= len hold zeros (see the shift below): they add +0 to the sum and stay zero in
-                        // the update, so neither loop needs a bound check and both are straight-line code
+                        // rolled steps: rows >= len hold zeros (see the shift below): they add +0 to the sum and stay zero
+                        // in the update, so neither loop needs a bound check and both are straight-line code
 #pragma unroll
-                        for (int i = 0; i < FSQ_NPIX; i++) { s += col[pass][i] * REFL(i); KA_ROWS(i); }
+                        for (int i = 0; i < LEN; i++) { s += col[pass][R0 + i] * REFL(i); KA_ROWS(i); }
                         if (FAST) {     // numerators REFL(i) * s: |REFL(i)| < 4, exponent >= emin_s (or zero)
                             const int es = fsq_expo(s);
                             KA_HZ(9, (emin_s + es - 2 < -FSQ_DIV_EN) || (es + 2 > FSQ_DIV_EN));
                         }
 #pragma unroll
-                        for (int i = 0; i < FSQ_NPIX; i++) { col[pass][i] = col[pass][i] - fsq_div_sel<FAST>(REFL(i) * s, kj); KA_ROWS(i); }
+                        for (int i = 0; i < (LAST ? 1 : LEN); i++) { col[pass][R0 + i] = col[pass][R0 + i] - fsq_div_sel<FAST>(REFL(i) * s, kj); KA_ROWS(i); }
                     }
-                    if (is_f) QL(Q_QTF, j) = col[pass][0];
-                    else if (nib_get(pos, slot) > j) QL(Q_R, j * 7 + slot) = col[pass][0];
+                    if (is_f) QL(Q_QTF, j) = col[pass][R0];
+                    else if (nib_get(pos, slot) > j) QL(Q_R, j * 7 + slot) = col[pass][R0];
                 }
                 // Norm down-dating of the live columns (mpfit.py:1810-1820).  It is scalar work per column, and at step j only
                 // the 6 - j columns at positions > j are live, scattered over the 8 slots of the group: the lanes take the live
@@ -922,7 +947,7 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     // are dealt out in order, lane cl taking j + 1 + cl and j + 1 + L + cl)
                     const int p = REGPOS ? cl + 4 * sub : j + 1 + cl + L * sub;
                     bool need = false;
-                    if (p > j && p < n7 && !broken && ajj0 != 0) {
+                    if (!LAST && p > j && p < n7 && !broken && ajj0 != 0) {
                         double rk = REGPOS ? prd[sub] : (double)QL(Q_RDIAG, p);
                         if (rk != 0 && !FAST) {
                             double temp = QL(Q_R, j * 7 + nib_get(ipvt, p)) / rk;
@@ -971,14 +996,21 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                 unsigned long long any_redo = 0ull;
 #pragma unroll
                 for (int sub = 0; sub < NSUB; sub++) any_redo |= redo[sub];
-                if (any_redo) {
+                if (!LAST && any_redo) {
 #pragma unroll
                     for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
                         const int slot = CMP ? my_slot : cl + L * pass;
                         const int k = (slot < 7) ? nib_get(pos, slot) : 0;
                         const int ix = REGPOS ? k : k - j - 1;      // (which lane looked at position k, and in which of its two turns)
                         if (slot < 7 && k > j && ((redo[(NSUB == 2) ? ix / L : 0] >> (gbase + ix % L)) & 1ull)) {
-                            const double rk = fsq_sqrt(dot_regcol_from1(col[pass], len));
+                            double rk;
+                            if (!ST) rk = fsq_sqrt(dot_regcol_from1(col[pass], len));
+                            else {
+                                double t[FSQ_NPIX];
+#pragma unroll
+                                for (int i = 0; i < FSQ_NPIX; i++) t[i] = (i < LEN) ? col[pass][R0 + i] : 0.0;
+                                rk = fsq_sqrt(dot_regcol_from1(t, len));
+                            }
                             QL(Q_WA, k) = rk;
                             QL(Q_RDIAG, k) = rk;
                             if (FAST) QL(Q_EPS, k) = 0.;            // an exact norm again
@@ -1000,18 +1032,25 @@ __global__ void __launch_bounds__(64, (L == 8 ? 4 : 2)) kA_jacobian(Ctx c, const
                     if (!broken) QL(Q_RDIAG, j) = QL(Q_TMP, 5);
                     QL(Q_R, j * 7 + lj) = QL(Q_RDIAG, j);           // fjac[j, lj] = rdiag[j] (mpfit.py:1123)
                 }
+                if (!ST) {
 #pragma unroll
-                for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
+                    for (int pass = 0; pass < (CMP ? 1 : NC); pass++) {
 #pragma unroll
-                    for (int i = 0; i + 1 < FSQ_NPIX; i++) col[pass][i] = col[pass][i + 1];
-                    col[pass][FSQ_NPIX - 1] = 0.0;
+                        for (int i = 0; i + 1 < FSQ_NPIX; i++) col[pass][i] = col[pass][i + 1];
+                        col[pass][FSQ_NPIX - 1] = 0.0;
+                    }
                 }
                 WAVE_SYNC();
                 RPH_MARK(11)
             };
-            for (int j = 0; j < (COMPACT ? 3 : n7); j++) qr_step(j, std::false_type{});
-            if (COMPACT)
+#define KA_STEP(J, CMPV) qr_step(std::integral_constant<int, J>{}, std::integral_constant<bool, CMPV>{})
+            if constexpr (QRS == 2) { KA_STEP(0, false); KA_STEP(1, false); KA_STEP(2, false); }
+            else
+                for (int j = 0; j < (COMPACT ? 3 : n7); j++) qr_step(j, std::false_type{});
+            if constexpr (QRS != 0) { KA_STEP(3, true); KA_STEP(4, true); KA_STEP(5, true); KA_STEP(6, true); }
+            else if (COMPACT)
                 for (int j = 3; j < n7; j++) qr_step(j, std::true_type{});
+#undef KA_STEP
             RPH_MARK(4)
             // ---- first iteration scaling, gradient test (mpfit.py:1099-1160) -----------------------
 #define QRG(i, k) QL(Q_R, (i) * 7 + nib_get(ipvt, (k)))
@@ -1942,11 +1981,11 @@ struct FsqFitQueue {
             slow_pending = 0;
         }
         if (gA > 0 && c.pix32)
-            hipLaunchKernelGGL((kA_jacobian<true, 4, true>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
+            hipLaunchKernelGGL((kA_jacobian<true, 4, true, FSQ_KA_QR_STATIC>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
         else if (gA > 0 && cfg.ka_lanes == 8)            // (kA also zeroes the counters of set nxt)
             hipLaunchKernelGGL((kA_jacobian<true, 8>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
         else if (gA > 0)
-            hipLaunchKernelGGL((kA_jacobian<true, 4>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
+            hipLaunchKernelGGL((kA_jacobian<true, 4, false, FSQ_KA_QR_STATIC>), dim3((unsigned)gA), dim3(64), cfg.ka_lds_pad, s, c, QA[cur], cset[cur] + CNT_A, QB[cur], cset[cur], SQ, cSlow, cset[nxt]);
         else
             FSQ_HIP_CHECK(hipMemsetAsync(cset[nxt], 0, CNT_SET * sizeof(int), s));
         // every fit in flight is in one of the six input lists of the step round by now (or terminated, or in the slow queue);
