@@ -1,0 +1,426 @@
+"""The proteome-scale Monte-Carlo of the reference's MCsimlib.py on the GPU: with these labels, this many Edman cycles and
+these error rates, which proteins of a proteome give a signal that no other protein gives?
+
+    peptides = attach(cleave(proteome, 'E'), 'C')                     # {protein: ((head, tail), ...)}
+    records = monte_carlo_records(peptides, p, b, u, windows, sample_size=1000, seed=7)
+    uniq = uniques_records(records, worst_ratio=10.0, absolute_min=5)
+    identifiable_proteins(uniq)                                       # {protein: number of its passing signals}
+
+WHAT IS BUILT.  cleave, attach, homogenize, homogenize_attached (:88-279), random_signal (:863-1074), SignalTrie (:1224-1547:
+add_descendant, get_descendant, leaf_iterator, count_nodes, find_uniques, find_uniques_absolute) and monte_carlo_trie
+(:1787-1849).  The device path (include/fsq_proteome_mc.h) is three kernels: fsq_proteome_signals samples every attached
+peptide sample_size times, one lane per sample, into 64-bit signal keys; fsq_proteome_tally counts (signal, protein) pairs in
+two open-addressing tables that stay on the device; fsq_proteome_uniques scans every signal's proteins as find_uniques does.
+host=True runs the NumPy twins of _host_proteome_mc instead; both give the same integers.  SignalTrie, monte_carlo_trie and
+random_signal are drop-ins built from the records, one Python object per signal: the slow path.
+
+ORDER CONTRACTS.  (1) Wherever the reference iterates `windows` - a dict, whose order Python 2 leaves open - this module
+iterates sorted(windows); a signal is a tuple sorted by position, then by acid in that order.  (2) Proteins are scanned in
+ascending protein index, the insertion order of `peptides`: the first-seen order of the reference's signal_count dicts when
+proteins are sampled one after the other, as monte_carlo_trie does.
+
+DRAW CONTRACT.  Sample first_sample + peptide_index * sample_size + j reads stream 3 of that item under `seed`
+(_host_peptide_sim.uniform; the peptide simulator uses streams 0 .. 2), in the order of the reference's random.random()
+calls: see _host_proteome_mc.  A result depends on (seed, first_sample, the order of peptides, sample_size) and on nothing
+else: not on chunk_rows, not on the table sizes.  The reference's monte_carlo_trie cannot run as shipped (its randsiggen C
+extension is not in its tree), so there is no draw-for-draw comparison with it; random_signal is compared draw for draw.
+
+LIMITS, each a NotImplementedError or ValueError that names it: the windows have at most 64 observable (position, acid)
+pairs (the 64-bit key) at positions 1 .. 63 for at most 8 acids; a peptide has at most 64 labelled residues, head and tail
+together, and a head of at most 255 residues; an Edman delay row (one per gap length d, under p) has at most 4 096 entries;
+signal_slots <= 2^27 and pair_slots <= 2^28, a table too small for the run raises ValueError naming the keyword.
+
+NOT BUILT: edman_failure_gaps, perfect, window_filter (the enumerating, non-Monte-Carlo route) and the Polyfluor* classes
+(peptide_simulator covers one label's chemistry); each raises NotImplementedError saying so.  discard, truncate_heads and the
+*_MP / monte_carlo_dictionary functions raise DeprecationWarning, as in the reference."""
+import ctypes
+import random as _random
+
+import numpy as np
+
+from . import _host_proteome_mc as H
+from ._host_proteome_mc import (attach, cleave, discard, edman_failure_gaps_MP, homogenize, homogenize_attached,     # noqa: F401
+                                monte_carlo_dictionary, monte_carlo_dictionary_MP, monte_carlo_trie_MP, truncate_heads,
+                                key_of, signal_of)
+
+DEFAULT_CHUNK_ROWS = 1 << 22
+
+
+def _not_built(name, why):
+    def f(*args, **kwargs):
+        raise NotImplementedError("%s is not built: %s" % (name, why))
+    f.__name__ = name
+    return f
+
+
+edman_failure_gaps = _not_built("edman_failure_gaps", "the enumerating route is out of scope; use monte_carlo_records")
+perfect = _not_built("perfect", "the enumerating route is out of scope (and perfect raises DeprecationWarning in the reference)")
+window_filter = _not_built("window_filter", "random_signal already applies the windows")
+PolyfluorSignal = _not_built("PolyfluorSignal", "peptide_simulator covers one label's chemistry")
+PolyfluorSignalTrie = _not_built("PolyfluorSignalTrie", "peptide_simulator covers one label's chemistry")
+PolyfluorPeptide = _not_built("PolyfluorPeptide", "peptide_simulator covers one label's chemistry")
+PolyfluorPeptide_v2 = _not_built("PolyfluorPeptide_v2", "peptide_simulator covers one label's chemistry")
+
+
+def _engine():
+    from . import engine
+    return engine
+
+
+def _native():
+    from . import _native_proteome_mc
+    return _native_proteome_mc
+
+
+def fresh_seed():
+    return _random.SystemRandom().getrandbits(63)
+
+
+# ---- tables ----
+
+def proteome_table(peptides, windows):
+    """Attached peptides {protein: ((head, tail), ...)} as the flat layout of _host_proteome_mc.peptide_table, proteins indexed
+    in dict order.  Raises for a peptide or windows beyond the limits."""
+    table = H.peptide_table(peptides, windows)
+    if not len(table["protein"]):
+        raise ValueError("no attached peptide")
+    return table
+
+
+def _as_table(peptides, windows):
+    return peptides if isinstance(peptides, dict) and "label_start" in peptides else proteome_table(peptides, windows)
+
+
+def _check_run(table, p, b, u, sample_size, seed, first_sample):
+    p, b, u, S = float(p), float(b), float(u), int(sample_size)
+    if not (0.0 <= p <= 1.0 and 0.0 <= u <= 1.0 and b >= 0.0):
+        raise ValueError("p and u must be in [0, 1] and b must not be negative")
+    if S < 1:
+        raise ValueError("sample_size must be positive")
+    total = len(table["protein"]) * S
+    if not 0 <= int(seed) < 1 << 64 or first_sample < 0 or first_sample + total > 1 << 64:
+        raise ValueError("seed and sample ids must be in 0 .. 2^64 - 1")
+    return p, b, u, S, total
+
+
+def _pow2_at_least(n):
+    return 1 << max(int(n) - 1, 0).bit_length()
+
+
+def device_table(table, p, b, device=None):
+    """The peptide table and the two chemistry tables (edman_table under p, bleach_table under b) as CUDA tensors."""
+    torch = _engine()._torch()
+    dev = torch.device(device or "cuda")
+    max_d = H.max_gap(table)
+    start, values = H.edman_table(p, max_d)
+    up = lambda a: torch.from_numpy(np.array(a)).to(dev)           # (a copy: the cached tables are read-only)
+    return {"protein": up(table["protein"]), "n_head": up(table["n_head"]), "label_start": up(table["label_start"]),
+            "labels": up(np.append(table["labels"], np.uint32(0)).view(np.int32)), "edman_start": up(start),
+            "edman": up(np.append(values, 0.0)), "bleach": up(H.bleach_table(b)), "max_d": max_d, "n_peptides": len(table["protein"]),
+            "layout": table["layout"], "device": dev}
+
+
+def signals_device(dtable, u, sample_size, seed, first_sample=0, first_row=0, n_rows=None, with_draws=False):
+    """fsq_proteome_signals: (key int64 [n_rows] holding the uint64 keys' bits, protein int32 [n_rows], n_draws int32 [n_rows] or
+    None).  Enqueued on the current stream, not synchronised."""
+    torch, NP = _engine()._torch(), _native()
+    layout, dev = dtable["layout"], dtable["device"]
+    n = dtable["n_peptides"] * int(sample_size) - int(first_row) if n_rows is None else int(n_rows)
+    prm = NP.FsqProteomeParams()
+    for a in range(len(layout.order)):
+        prm.E[a], prm.O[a], prm.base[a] = layout.E[a], layout.O[a], layout.base[a]
+    prm.n_acids, prm.max_d, prm.u = len(layout.order), dtable["max_d"], float(u)
+    prm.seed, prm.first_sample, prm.sample_size = int(seed), int(first_sample), int(sample_size)
+    key = torch.empty(max(n, 0), dtype=torch.int64, device=dev)
+    protein = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    draws = torch.empty(max(n, 0), dtype=torch.int32, device=dev) if with_draws else None
+    _engine().launch(NP.lib().fsq_proteome_signals, "fsq_proteome_signals", dev, ctypes.byref(prm), dtable["protein"].data_ptr(),
+                     dtable["n_head"].data_ptr(), dtable["label_start"].data_ptr(), dtable["labels"].data_ptr(), dtable["n_peptides"],
+                     dtable["edman_start"].data_ptr(), dtable["edman"].data_ptr(), dtable["bleach"].data_ptr(), int(first_row), n,
+                     key.data_ptr() if n > 0 else None, protein.data_ptr() if n > 0 else None,
+                     draws.data_ptr() if with_draws and n > 0 else None)
+    return key, protein, draws
+
+
+def new_tables(signal_slots, pair_slots, device):
+    """The empty tables of fsq_proteome_tally: signals int64 [signal_slots] (0: free), pairs int64 [pair_slots] (-1: free), counts
+    int64 [pair_slots], overflow int32 [2]."""
+    torch, NP = _engine()._torch(), _native()
+    sa, sb = int(signal_slots), int(pair_slots)
+    if sa < 1 or sa & (sa - 1) or sa > NP.MAX_SIGNAL_SLOTS:
+        raise ValueError("signal_slots=%d must be a power of two up to 2^27" % sa)
+    if sb < 1 or sb & (sb - 1) or sb > NP.MAX_PAIR_SLOTS:
+        raise ValueError("pair_slots=%d must be a power of two up to 2^28" % sb)
+    return {"signals": torch.zeros(sa, dtype=torch.int64, device=device), "pairs": torch.full((sb,), -1, dtype=torch.int64, device=device),
+            "counts": torch.zeros(sb, dtype=torch.int64, device=device), "overflow": torch.zeros(2, dtype=torch.int32, device=device)}
+
+
+def tally_device(tables, d_key, d_protein):
+    """fsq_proteome_tally: adds (key, protein) rows (int64 key bits [n], int32 [n]) to the tables.  Enqueued, not synchronised."""
+    torch, NP = _engine()._torch(), _native()
+    n = int(d_key.shape[0])
+    if d_key.dtype != torch.int64 or d_protein.dtype != torch.int32 or tuple(d_protein.shape) != (n,) or d_key.dim() != 1:
+        raise ValueError("int64 keys [n] and int32 proteins [n] are needed")
+    if not (d_key.is_contiguous() and d_protein.is_contiguous()):
+        raise ValueError("contiguous tensors are needed")
+    _engine().launch(NP.lib().fsq_proteome_tally, "fsq_proteome_tally", d_key.device, d_key.data_ptr() if n else None,
+                     d_protein.data_ptr() if n else None, n, tables["signals"].data_ptr(), int(tables["signals"].shape[0]),
+                     tables["pairs"].data_ptr(), tables["counts"].data_ptr(), int(tables["pairs"].shape[0]),
+                     tables["overflow"].data_ptr())
+
+
+def check_tables(tables):
+    over = tables["overflow"].cpu().tolist()
+    if over[0]:
+        raise ValueError("more distinct signals than signal_slots=%d: pass a larger power of two" % int(tables["signals"].shape[0]))
+    if over[1]:
+        raise ValueError("more distinct (signal, protein) pairs than pair_slots=%d: pass a larger power of two" % int(tables["pairs"].shape[0]))
+
+
+def pairs_device(tables):
+    """The occupied pairs of table B, sorted by (key as uint64, protein): key int64 (bits), protein int32, count int64, and
+    segment int64 [n_signals + 1], the starts of the signals."""
+    torch = _engine()._torch()
+    occupied = tables["pairs"] != -1
+    pair, count = tables["pairs"][occupied], tables["counts"][occupied]
+    key, protein = tables["signals"][pair >> 32], pair & 0xffffffff
+    order = torch.sort(protein, stable=True)[1]
+    order = order[torch.sort((key ^ (-1 << 63))[order], stable=True)[1]]
+    key, protein, count = key[order].contiguous(), protein[order].to(torch.int32).contiguous(), count[order].contiguous()
+    n = int(key.shape[0])
+    new = torch.ones(n, dtype=torch.bool, device=key.device)
+    if n > 1:
+        new[1:] = key[1:] != key[:-1]
+    segment = torch.cat([new.nonzero().reshape(-1), torch.tensor([n], dtype=torch.int64, device=key.device)]).contiguous()
+    return key, protein, count, segment
+
+
+def uniques_device(d_protein, d_count, d_segment, modes, demote=False):
+    """fsq_proteome_uniques over sorted pairs: a dict of CUDA tensors [n_signals] named as _host_proteome_mc.UNIQUE_FIELDS."""
+    torch, NP = _engine()._torch(), _native()
+    n = int(d_segment.shape[0]) - 1
+    dev = d_segment.device
+    prm = NP.FsqUniquesParams()
+    prm.ratio_mode, prm.worst_ratio, prm.absolute_min, prm.has_maximum_secondary, prm.maximum_secondary = modes
+    prm.demote = int(bool(demote))
+    tt = {np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8}
+    out = {name: torch.empty(max(n, 0), dtype=tt[dtype], device=dev) for name, dtype in H.UNIQUE_FIELDS}
+    ptr = lambda t: t.data_ptr() if n > 0 else None
+    _engine().launch(NP.lib().fsq_proteome_uniques, "fsq_proteome_uniques", dev, ptr(d_protein), ptr(d_count), ptr(d_segment), n,
+                     ctypes.byref(prm), *[ptr(out[name]) for name, _ in H.UNIQUE_FIELDS])
+    return out
+
+
+# ---- the run ----
+
+def monte_carlo_device(table, p, b, u, sample_size, seed, first_sample=0, chunk_rows=DEFAULT_CHUNK_ROWS, signal_slots=None,
+                       pair_slots=None, device=None):
+    """Sample every peptide of `table` (proteome_table) sample_size times and count (signal, protein) pairs, in chunks of at most
+    chunk_rows samples (the result does not depend on it); everything stays on the device.  Returns a dict: `tables`
+    (new_tables), `names`, `layout`, `rows`.
+    signal_slots (table A, 8 bytes a slot) and pair_slots (table B, 16 bytes a slot) are powers of two; by default both are the
+    power of two at or above twice the number of samples, A at most 2^26 (512 MiB) and B at most 2^26 (1 GiB): a run cannot
+    have more distinct signals or pairs than samples, so the defaults overflow only beyond 2^25 samples.  A table that turns
+    out too small raises ValueError naming its keyword."""
+    torch = _engine()._torch()
+    p, b, u, S, total = _check_run(table, p, b, u, sample_size, seed, first_sample)
+    chunk = int(chunk_rows)
+    if chunk < 1:
+        raise ValueError("chunk_rows must be positive")
+    dtable = device_table(table, p, b, device)
+    default = min(max(_pow2_at_least(2 * total), 1024), 1 << 26)
+    tables = new_tables(default if signal_slots is None else signal_slots, default if pair_slots is None else pair_slots,
+                        dtable["device"])
+    for first in range(0, total, chunk):
+        key, protein, _ = signals_device(dtable, u, S, seed, first_sample, first, min(chunk, total - first))
+        tally_device(tables, key, protein)
+    check_tables(tables)
+    return {"tables": tables, "names": table["names"], "layout": table["layout"], "rows": total}
+
+
+def monte_carlo_records(peptides, p, b, u, windows=None, sample_size=100, seed=0, first_sample=0, chunk_rows=DEFAULT_CHUNK_ROWS,
+                        signal_slots=None, pair_slots=None, device=None, host=False):
+    """The (signal, protein) counts of a run as NumPy arrays sorted by (key, protein): a dict with key uint64, protein int32,
+    count int64, names (proteins in index order) and layout (the key's).  `peptides` is an attached-peptide dict (with
+    `windows`) or a proteome_table."""
+    table = _as_table(peptides, windows)
+    if host:
+        p, b, u, S, total = _check_run(table, p, b, u, sample_size, seed, first_sample)
+        keys, _ = H.signals(table, p, b, u, S, seed, first_sample)
+        k, pr, c = H.tally(keys, H.row_proteins(table, S, 0, total))
+    else:
+        run = monte_carlo_device(table, p, b, u, sample_size, seed, first_sample, chunk_rows, signal_slots, pair_slots, device)
+        key, protein, count, _ = pairs_device(run["tables"])
+        k, pr, c = key.cpu().numpy().view(np.uint64), protein.cpu().numpy(), count.cpu().numpy()
+    return {"key": k, "protein": pr, "count": c, "names": list(table["names"]), "layout": table["layout"]}
+
+
+def _uniques_any(source, modes, demote, host, device):
+    if "tables" in source:                                  # a monte_carlo_device result
+        if host:
+            raise ValueError("host=True needs records, not a device result")
+        key, protein, count, segment = pairs_device(source["tables"])
+    elif host:
+        out = H._uniques((source["key"], source["protein"], source["count"]), modes, demote)
+        out.update(names=source["names"], layout=source["layout"], demote=bool(demote),
+                   triples=(source["key"], source["protein"], source["count"]))
+        return out
+    else:
+        torch = _engine()._torch()
+        dev = torch.device(device or "cuda")
+        key = torch.from_numpy(np.ascontiguousarray(source["key"]).view(np.int64)).to(dev)
+        protein = torch.from_numpy(np.ascontiguousarray(source["protein"], np.int32)).to(dev)
+        count = torch.from_numpy(np.ascontiguousarray(source["count"], np.int64)).to(dev)
+        segment = torch.from_numpy(H.segments(source["key"])).to(dev)
+    got = uniques_device(protein, count, segment, modes, demote)
+    out = {name: t.cpu().numpy() for name, t in got.items()}
+    triples = (key.cpu().numpy().view(np.uint64), protein.cpu().numpy(), count.cpu().numpy())
+    out["segment"] = segment.cpu().numpy()
+    out["key"] = triples[0][out["segment"][:-1]]
+    out.update(names=source["names"], layout=source["layout"], demote=bool(demote), triples=triples)
+    return out
+
+
+def uniques_records(records_or_device, worst_ratio, absolute_min, maximum_secondary=None, demote=False, host=False, device=None):
+    """find_uniques' scan for every signal of monte_carlo_records' or monte_carlo_device's result: the arrays of
+    _host_proteome_mc.uniques (key, best_protein, best_count, second_protein, second_count, n_ties, tertiary, passed, segment)
+    plus names, layout and the sorted triples.  demote=True is an extension: the true top two."""
+    return _uniques_any(records_or_device, H.scan_modes(worst_ratio, absolute_min, maximum_secondary), demote, host, device)
+
+
+def uniques_absolute_records(records_or_device, minimum_best, maximum_secondary, demote=False, host=False, device=None):
+    """find_uniques_absolute's scan, as uniques_records."""
+    return _uniques_any(records_or_device, H.scan_modes(None, minimum_best, maximum_secondary, absolute=True), demote, host, device)
+
+
+def uniques_dict(uniq):
+    """The reference's dict of the passing signals of a uniques_records result."""
+    return H.unique_dict(uniq, uniq["triples"], uniq["layout"], uniq["names"], uniq["demote"])
+
+
+def identifiable_proteins(uniq):
+    """{protein: the number of passing signals for which it is best}, proteins in index order."""
+    best = uniq["best_protein"][uniq["passed"] != 0]
+    n = np.bincount(best, minlength=len(uniq["names"]))
+    return {uniq["names"][i]: int(n[i]) for i in np.flatnonzero(n).tolist()}
+
+
+# ---- drop-ins ----
+
+class SignalTrie(object):
+    """The reference's prefix tree of signals (:1224-1547): a node is a (position, acid) block, holds its descendants and
+    signal_count = {protein: count}.  The root is SignalTrie((None, None))."""
+
+    def __init__(self, block):
+        self.signal_block = tuple(block)
+        self.descendants = {}
+        self.signal_count = {}
+
+    def add_descendant(self, subsignal, source_protein, count=1):
+        """:1252-1281 (`count` more at once is this module's: the records arrive counted)."""
+        if len(subsignal) == 0:
+            return
+        elif self.signal_block == (None, None):
+            self.descendants.setdefault(subsignal[0], SignalTrie(subsignal[0]))
+            self.descendants[subsignal[0]].add_descendant(subsignal, source_protein, count)
+        elif len(subsignal) == 1:
+            self.signal_count.setdefault(source_protein, 0)
+            self.signal_count[source_protein] += count
+        else:
+            self.descendants.setdefault(subsignal[1], SignalTrie(subsignal[1]))
+            self.descendants[subsignal[1]].add_descendant(subsignal[1:], source_protein, count)
+        return self
+
+    def get_descendant(self, subsignal):
+        """:1308-1335."""
+        if len(subsignal) == 0:
+            return
+        elif self.signal_block == (None, None):
+            if subsignal[0] in self.descendants:
+                return self.descendants[subsignal[0]].get_descendant(subsignal)
+            return None
+        elif len(subsignal) == 1:
+            return self
+        elif subsignal[1] in self.descendants:
+            return self.descendants[subsignal[1]].get_descendant(subsignal[1:])
+        return None
+
+    def _iterate(self, every):
+        for d_trie in self.descendants.values():
+            for node in d_trie._iterate(every):
+                if self.signal_block == (None, None):
+                    yield node
+                else:
+                    yield ((self.signal_block,) + node[0], node[1], node[2])
+        if every or len(self.signal_count) > 0:
+            yield ((self.signal_block,), self.signal_count, self)
+
+    def node_iterator(self):
+        """:1336-1357."""
+        return self._iterate(True)
+
+    def leaf_iterator(self):
+        """:1375-1397."""
+        return self._iterate(False)
+
+    def count_nodes(self):
+        """:1533-1547: (empty nodes, used nodes)."""
+        empty = used = 0
+        for leaf in self.node_iterator():
+            if len(leaf[1]) == 0:
+                empty += 1
+            else:
+                used += 1
+        return empty, used
+
+    def _find(self, modes):
+        out = {}
+        for signal, signal_count, _ in self.leaf_iterator():
+            names = list(signal_count)
+            bp, bc, sp, sc, _, tertiary, passed = H.scan_counts(list(enumerate(signal_count.values())), *modes, False)
+            if passed:
+                second = (names[sp] if sp >= 0 else None, sc)
+                ties = [(name, c) for name, c in signal_count.items() if c == sc and name != second[0]]
+                out[signal] = [(names[bp], bc), [second] + ties, tertiary]
+        return out
+
+    def find_uniques(self, worst_ratio, absolute_min, maximum_secondary=None):
+        """:1398-1486, every node's signal_count scanned in its dict's order."""
+        return self._find(H.scan_modes(worst_ratio, absolute_min, maximum_secondary))
+
+    def find_uniques_absolute(self, minimum_best, maximum_secondary):
+        """:1487-1532."""
+        return self._find(H.scan_modes(None, minimum_best, maximum_secondary, absolute=True))
+
+
+def trie_of_records(records):
+    """A SignalTrie holding the records' counts, signals added in (key, protein) order."""
+    trie = SignalTrie((None, None))
+    layout, names = records["layout"], records["names"]
+    signal, last = None, None
+    for key, protein, count in zip(records["key"].tolist(), records["protein"].tolist(), records["count"].tolist()):
+        if key != last:
+            signal, last = signal_of(key, layout), key
+        trie.add_descendant(signal, names[protein], count)
+    return trie
+
+
+def monte_carlo_trie(peptides, p, b, u, windows, sample_size=100, random_seed=None, silent=True, host=False, **run):
+    """:1787-1849: the SignalTrie of sample_size signals per attached peptide.  random_seed=None draws a fresh seed; an int
+    reproduces a run (under this module's draw contract, not the reference's random.seed)."""
+    seed = fresh_seed() if random_seed is None else int(random_seed)
+    if not silent:
+        print("monte_carlo_trie: seed %d" % seed)
+    return trie_of_records(monte_carlo_records(peptides, p, b, u, windows, sample_size, seed, host=host, **run))
+
+
+def random_signal(peptide, p=1.0, b=0.0, u=0.0, windows={}, seed=None, sample=0, host=False, device=None):
+    """:863-1074 for one sample: the signal of sample id `sample` under `seed` (None: a fresh seed)."""
+    seed = fresh_seed() if seed is None else int(seed)
+    if host:
+        H.layout_of(windows)
+        return H.sample_signal(peptide, p, b, u, windows, seed, int(sample))[0]
+    table = proteome_table({"": (tuple(peptide),)}, windows)
+    p, b, u, _, _ = _check_run(table, p, b, u, 1, seed, int(sample))
+    key, _, _ = signals_device(device_table(table, p, b, device), u, 1, seed, int(sample))
+    return signal_of(int(key.cpu().numpy().view(np.uint64)[0]), table["layout"])
