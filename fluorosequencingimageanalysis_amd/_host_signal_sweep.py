@@ -1,7 +1,8 @@
 """The host twin of the simulation parameter sweep (include/fsq_signal_sweep.h), NumPy and plain Python: the 64-bit signal
 key and its codec, the classification and tally of count rows, the key table a scoring call is made over and
 signal_correlation (jupyter_development.py:279-578) for many fit dicts at once, in the kernel's order of operations, so that
-fsq_signal_scores can be compared with it bit for bit.  No GPU and no torch are needed."""
+fsq_signal_scores can be compared with it bit for bit, and match_diagnostic's loop over signal pairs (:833-889) as
+fsq_signal_pair_best and fsq_signal_pair_extremes run it.  No GPU and no torch are needed."""
 import math
 
 import numpy as np
@@ -158,6 +159,57 @@ def fit_matrix(signals, fit_dicts):
 
 # ---- the scores ----
 
+def term(m, oi, fi, nf, n_obs, n_fit):
+    """One paired key's contribution under metric index m and the factor nf, as fsq_score_term.h's score_term: (c, is_max,
+    error).  c is None where the metric takes no contribution from the key; error is 0, SCORE_DIVZERO or SCORE_DOMAIN."""
+    o, f = float(oi), float(fi) * nf
+    if m == 0:
+        return o * f, False, 0
+    if m == 1:
+        return (f - o) ** 2, False, 0
+    if m in (2, 8):
+        if oi <= 0:
+            return None, m == 8, 0
+        return (((f - o) / o) ** 2 if m == 2 else abs(o - f) / o), m == 8, 0
+    if m in (3, 4, 9):
+        sd = 1.0
+        if m == 4:
+            if f > 0.0:
+                v = f * (float(n_fit) - f) / float(n_fit)
+                if v < 0.0:
+                    return None, False, SCORE_DOMAIN
+                sd = math.sqrt(v)
+        elif oi > 0:
+            if n_obs == 0:
+                return None, False, SCORE_DIVZERO
+            v = float(oi * (n_obs - oi)) / float(n_obs)
+            if v < 0.0:
+                return None, False, SCORE_DOMAIN
+            sd = math.sqrt(v)
+        if sd == 0.0:
+            return None, False, SCORE_DIVZERO
+        return (((f - o) / sd) ** 2 if m != 9 else abs(o - f) / sd), m == 9, 0
+    if m == 5:
+        return (math.log(float(oi + 1)) - math.log(f + 1.0)) ** 2, False, 0
+    if m == 6:
+        den = abs(o) + abs(f)
+        if den == 0.0:
+            return None, False, SCORE_DIVZERO
+        return abs(o - f) / den, False, 0
+    return abs(o - f), True, 0
+
+
+def result(m, acc, n_contrib, divzero, domain):
+    """(status, result) of the accumulated terms, as fsq_score_term.h's score_result after the error flags."""
+    if domain or divzero or (m == 8 and n_contrib == 0):
+        return (SCORE_DIVZERO if divzero and not domain else SCORE_DOMAIN), None
+    return SCORE_OK, acc if m in (0, 6, 7, 8, 9) else math.sqrt(acc / float(n_contrib)) if m == 5 else math.sqrt(acc)
+
+
+def is_paired(adm, in_obs, o, f, cutoff):
+    return bool(adm and (in_obs or f > 0) and (cutoff is None or (float(o) >= cutoff and float(f) >= cutoff)))
+
+
 def scores(table, fit, fit_total, metric, normalization=0, small_count_cutoff=None, contributions=True):
     """fsq_signal_scores on the host, operation for operation: (score float64 [P], factor float64 [P], status int32 [P],
     contributions float64 [S][P] or None), NaN where the kernel writes NaN."""
@@ -172,8 +224,7 @@ def scores(table, fit, fit_total, metric, normalization=0, small_count_cutoff=No
     cutoff = None if small_count_cutoff is None else float(small_count_cutoff)
     for k in range(P):
         f_k, n_fit = fit[:, k].tolist(), int(fit_total[k])
-        pairs = [i for i in range(S) if adm[i] and (in_obs[i] or f_k[i] > 0)
-                 and (cutoff is None or (float(obs[i]) >= cutoff and float(f_k[i]) >= cutoff))]
+        pairs = [i for i in range(S) if is_paired(adm[i], in_obs[i], obs[i], f_k[i], cutoff)]
         sum_o, sum_f = sum(obs[i] for i in pairs), sum(f_k[i] for i in pairs)
         nf = 1.0
         if (normalization & NORMALIZE_COUNTS) and pairs and sum_f > 0:
@@ -191,56 +242,17 @@ def scores(table, fit, fit_total, metric, normalization=0, small_count_cutoff=No
             continue
         acc, n_contrib, divzero, domain = 0.0, 0, False, False
         for i in pairs:
-            oi, o, f = obs[i], float(obs[i]), float(f_k[i]) * nf
-            is_max = False
-            if m == 0:
-                c = o * f
-            elif m == 1:
-                c = (f - o) ** 2
-            elif m in (2, 8):
-                if oi <= 0:
-                    continue
-                c, is_max = ((f - o) / o) ** 2 if m == 2 else abs(o - f) / o, m == 8
-            elif m in (3, 4, 9):
-                sd = 1.0
-                if m == 4:
-                    if f > 0.0:
-                        v = f * (float(n_fit) - f) / float(n_fit)
-                        if v < 0.0:
-                            domain = True
-                            continue
-                        sd = math.sqrt(v)
-                elif oi > 0:
-                    if n_obs == 0:
-                        divzero = True
-                        continue
-                    v = float(oi * (n_obs - oi)) / float(n_obs)
-                    if v < 0.0:
-                        domain = True
-                        continue
-                    sd = math.sqrt(v)
-                if sd == 0.0:
-                    divzero = True
-                    continue
-                c, is_max = ((f - o) / sd) ** 2 if m != 9 else abs(o - f) / sd, m == 9
-            elif m == 5:
-                c = (math.log(float(oi + 1)) - math.log(f + 1.0)) ** 2
-            elif m == 6:
-                den = abs(o) + abs(f)
-                if den == 0.0:
-                    divzero = True
-                    continue
-                c = abs(o - f) / den
-            else:
-                c, is_max = abs(o - f), True
+            c, is_max, err = term(m, obs[i], f_k[i], nf, n_obs, n_fit)
+            divzero, domain = divzero or err == SCORE_DIVZERO, domain or err == SCORE_DOMAIN
+            if c is None:
+                continue
             n_contrib += 1
             if contrib is not None:
                 contrib[i, k] = c
             acc = max(acc, c) if is_max else acc + c
-        if domain or divzero or (m == 8 and n_contrib == 0):
-            status[k] = SCORE_DIVZERO if divzero and not domain else SCORE_DOMAIN
-            continue
-        score[k] = acc if m in (0, 6, 7, 8, 9) else math.sqrt(acc / float(n_contrib)) if m == 5 else math.sqrt(acc)
+        status[k], r = result(m, acc, n_contrib, divzero, domain)
+        if status[k] == SCORE_OK:
+            score[k] = r
     return score, factor, status, contrib
 
 
@@ -255,3 +267,95 @@ def result_of(signals, score, factor, status, contrib, k):
         return None, (float(factor[k]), {})
     c = {} if contrib is None else {s: float(contrib[i][k]) for i, s in enumerate(signals) if contrib[i][k] == contrib[i][k]}
     return float(score[k]), (float(factor[k]), c)
+
+
+# ---- the incompatibility loop over signal pairs (jupyter_development.py:838-889) ----
+
+MAX_SEL = 2048                      # FSQ_SIGNAL_PAIR_MAX_SEL
+
+
+def pair_index(i, j, n_sel):
+    """The index of pair (i, j), i < j, in itertools.combinations' order."""
+    return i * (2 * n_sel - i - 1) // 2 + j - i - 1
+
+
+def heat_factors(table, fit, fit_total):
+    """The points' heat-map factor and status, which do not depend on the pair: scores() with nothing admitted."""
+    none = dict(table, admitted=np.zeros_like(table["admitted"]))
+    _, factor, status, _ = scores(none, fit, fit_total, METRICS[0], HEATMAP_NORMALIZE_COUNTS, None, False)
+    return factor, status
+
+
+def pair_best(table, rows, fit, fit_total, metric, normalization=0, small_count_cutoff=None, reverse_order=False):
+    """fsq_signal_pair_best on the host, operation for operation: a dict of best_point int32 [K], result, factor float64 [K],
+    dist float64 [K, 2], error_point and error_status int32 [K] for the K pairs of the candidates whose rows in the key table
+    are `rows` (-1: in no dict)."""
+    m = check_metric(metric)
+    obs, in_obs, adm = (table[k].tolist() for k in ("observed", "in_observed", "admitted"))
+    S, n_obs, P = len(obs), table["n_observed"], len(fit_total)
+    rows = [int(r) for r in rows]
+    n_sel = len(rows)
+    if not 2 <= n_sel <= MAX_SEL or P < 1 or any(not -1 <= r < S for r in rows):
+        raise ValueError("2 .. %d candidate rows within -1 .. n_keys - 1 and at least one point are needed" % MAX_SEL)
+    fit = np.asarray(fit, dtype=np.int64).reshape(S, P).tolist()
+    totals = [int(n) for n in fit_total]
+    cutoff = None if small_count_cutoff is None else float(small_count_cutoff)
+    heat_f, heat_s = heat_factors(table, fit, fit_total) if normalization & HEATMAP_NORMALIZE_COUNTS else (None, None)
+    K = n_sel * (n_sel - 1) // 2
+    out = {"best_point": np.full(K, -1, np.int32), "result": np.full(K, np.nan), "factor": np.full(K, np.nan),
+           "dist": np.full((K, 2), np.nan), "error_point": np.full(K, -1, np.int32), "error_status": np.zeros(K, np.int32)}
+    t = -1
+    for i in range(n_sel):
+        for j in range(i + 1, n_sel):
+            t += 1
+            pair = [r for r in (rows[i], rows[j])]
+            best = None
+            for k in range(P):
+                f = [fit[r][k] if r >= 0 and adm[r] else 0 for r in pair]
+                pr = [r >= 0 and is_paired(adm[r], in_obs[r], obs[r], f[x], cutoff) for x, r in enumerate(pair)]
+                sum_o, sum_f = sum(obs[r] for x, r in enumerate(pair) if pr[x]), sum(f[x] for x in range(2) if pr[x])
+                nf, status = 1.0, SCORE_OK
+                if (normalization & NORMALIZE_COUNTS) and any(pr) and sum_f > 0:
+                    nf = float(sum_o) / float(sum_f)
+                elif normalization & HEATMAP_NORMALIZE_COUNTS:
+                    if heat_s[k] == SCORE_DIVZERO:
+                        status = SCORE_DIVZERO
+                    else:
+                        nf = float(heat_f[k])
+                if status == SCORE_OK and not any(pr):
+                    status = SCORE_EMPTY
+                d, r = [np.nan, np.nan], None
+                if status == SCORE_OK:
+                    acc, n_contrib, divzero, domain = 0.0, 0, False, False
+                    for x in range(2):
+                        if not pr[x]:
+                            continue
+                        c, is_max, err = term(m, obs[pair[x]], f[x], nf, n_obs, totals[k])
+                        divzero, domain = divzero or err == SCORE_DIVZERO, domain or err == SCORE_DOMAIN
+                        if c is None:
+                            continue
+                        n_contrib += 1
+                        d[x] = c
+                        acc = max(acc, c) if is_max else acc + c
+                    status, r = result(m, acc, n_contrib, divzero, domain)
+                if status == SCORE_OK:
+                    if best is None or (r > best[0] if reverse_order else r < best[0]):
+                        best = (r, k, nf, d)
+                elif status != SCORE_EMPTY and out["error_point"][t] < 0:
+                    out["error_point"][t], out["error_status"][t] = k, status
+            if best is not None:
+                out["result"][t], out["best_point"][t], out["factor"][t], out["dist"][t] = best
+    return out
+
+
+def pair_extremes(dist, n_sel, reverse_order=False):
+    """fsq_signal_pair_extremes on the host: (score float64 [n_sel], n_distances int32 [n_sel]); the maximum (the minimum with
+    reverse_order) of each candidate's n_sel - 1 distances, NaN skipped, NaN where there is none."""
+    dist = np.asarray(dist, dtype=np.float64).reshape(-1, 2)
+    if not 2 <= n_sel <= MAX_SEL or len(dist) != n_sel * (n_sel - 1) // 2:
+        raise ValueError("2 .. %d candidates and a [n_sel (n_sel - 1) / 2, 2] array are needed" % MAX_SEL)
+    i, j = np.triu_indices(n_sel, 1)                                    # combinations' order
+    mine = np.full((n_sel, n_sel), np.nan)
+    mine[i, j], mine[j, i] = dist[:, 0], dist[:, 1]
+    score = (np.fmin if reverse_order else np.fmax).reduce(mine, axis=1)
+    return score, (~np.isnan(mine)).sum(axis=1).astype(np.int32)

@@ -11,6 +11,7 @@ EMPTY = 0x400                       # FSQ_SIGNAL_EMPTY
 NEVER = 0x800                       # FSQ_SIGNAL_NEVER
 MAX_SLOTS = 1 << 24                 # FSQ_SIGNAL_MAX_SLOTS
 MAX_COUNT = (1 << 31) - 1           # what fsq_signal_scores takes as a count
+MAX_SEL = 2048                      # FSQ_SIGNAL_PAIR_MAX_SEL
 
 METRICS = ('naive', 'my_euclidean', 'normalized_euclidean', 'my_std_normalized_euclidean', 'my_sim_std_normalized_euclidean',
            'log_rmsd', 'my_canberra', 'my_chebyshev', 'my_normalized_chebyshev', 'my_std_normalized_chebyshev')   # FSQ_SCORE_*
@@ -36,6 +37,9 @@ _SIGS = {
     "fsq_signal_tally": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "fsq_signal_lookup": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "fsq_signal_scores": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.POINTER(FsqScoreParams), _P, _P, _P, _P, _P]),
+    "fsq_signal_pair_best": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, ctypes.POINTER(FsqScoreParams), _P, _I32, _I32, _P, _P,
+                                            _P, _P, _P, _P, _P, _P, _P]),
+    "fsq_signal_pair_extremes": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P]),
 }
 EXPORTED = tuple(_SIGS)
 

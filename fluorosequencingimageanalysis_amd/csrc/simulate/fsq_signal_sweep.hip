@@ -17,6 +17,7 @@
 #include "../libm/fsq_glibc_pow.h"
 #include "fsq_philox.h"
 #include "fsq_peptide_lane.h"
+#include "fsq_score_term.h"
 
 namespace {
 
@@ -207,10 +208,7 @@ kss_scores(const long long* __restrict__ g_obs, const uint8_t* __restrict__ g_in
     if (k >= P) return;
     const double nan = __builtin_nan("");
     const int metric = prm.metric;
-    auto paired = [&](int i, long long o, long long f) {
-        if (!g_admitted[i] || !(g_in_obs[i] || f > 0)) return false;
-        return !prm.has_cutoff || ((double)o >= prm.small_count_cutoff && (double)f >= prm.small_count_cutoff);
-    };
+    auto paired = [&](int i, long long o, long long f) { return score_paired(prm, g_admitted[i], g_in_obs[i], o, f); };
     if (g_contrib)
         for (int i = 0; i < S; ++i) g_contrib[(long long)i * P + k] = nan;
     g_score[k] = nan;
@@ -242,7 +240,7 @@ kss_scores(const long long* __restrict__ g_obs, const uint8_t* __restrict__ g_in
         g_status[k] = FSQ_SCORE_EMPTY;
         return;
     }
-    // the contributions (:364-503), in key order
+    // the contributions (:364-503), in key order: the terms are fsq_score_term.h's
     const long long n_obs = prm.n_observed, n_fit = g_fit_total[k];
     double acc = 0.0;
     int n_contrib = 0;
@@ -250,94 +248,22 @@ kss_scores(const long long* __restrict__ g_obs, const uint8_t* __restrict__ g_in
     for (int i = 0; i < S; ++i) {
         const long long oi = g_obs[i], fi = g_fit[(long long)i * P + k];
         if (!paired(i, oi, fi)) continue;
-        const double o = (double)oi, f = (double)fi * factor;
-        double c = 0.0;
-        bool have = true, is_max = false;
-        switch (metric) {
-        case FSQ_SCORE_NAIVE:
-            c = o * f;
-            break;
-        case FSQ_SCORE_MY_EUCLIDEAN:
-            c = sf_pow<2, true>(f - o);
-            break;
-        case FSQ_SCORE_NORMALIZED_EUCLIDEAN:
-            if (oi > 0) c = sf_pow<2, true>((f - o) / o);
-            else have = false;
-            break;
-        case FSQ_SCORE_MY_STD_NORMALIZED_EUCLIDEAN:
-        case FSQ_SCORE_MY_STD_NORMALIZED_CHEBYSHEV: {
-            double sd = 1.0;
-            if (oi > 0) {
-                if (n_obs == 0) { divzero = true; have = false; break; }
-                const double v = (double)(oi * (n_obs - oi)) / (double)n_obs;
-                if (v < 0.0) { domain = true; have = false; break; }
-                sd = sqrt(v);
-            }
-            if (sd == 0.0) { divzero = true; have = false; break; }
-            if (metric == FSQ_SCORE_MY_STD_NORMALIZED_EUCLIDEAN) c = sf_pow<2, true>((f - o) / sd);
-            else { c = fabs(o - f) / sd; is_max = true; }
-            break;
-        }
-        case FSQ_SCORE_MY_SIM_STD_NORMALIZED_EUCLIDEAN: {
-            double sd = 1.0;
-            if (f > 0.0) {
-                const double v = f * ((double)n_fit - f) / (double)n_fit;
-                if (v < 0.0) { domain = true; have = false; break; }
-                sd = sqrt(v);
-            }
-            if (sd == 0.0) { divzero = true; have = false; break; }
-            c = sf_pow<2, true>((f - o) / sd);
-            break;
-        }
-        case FSQ_SCORE_LOG_RMSD:
-            c = sf_pow<2, true>(ln_log((double)(oi + 1)) - ln_log(f + 1.0));
-            break;
-        case FSQ_SCORE_MY_CANBERRA: {
-            const double den = fabs(o) + fabs(f);
-            if (den == 0.0) { divzero = true; have = false; break; }
-            c = fabs(o - f) / den;
-            break;
-        }
-        case FSQ_SCORE_MY_CHEBYSHEV:
-            c = fabs(o - f);
-            is_max = true;
-            break;
-        default:                                                                    // FSQ_SCORE_MY_NORMALIZED_CHEBYSHEV
-            if (oi > 0) { c = fabs(o - f) / o; is_max = true; }
-            else have = false;
-            break;
-        }
-        if (!have) continue;
+        const ScoreTerm t = score_term(metric, oi, fi, factor, n_obs, n_fit);
+        divzero |= t.divzero;
+        domain |= t.domain;
+        if (!t.have) continue;
         ++n_contrib;
-        if (g_contrib) g_contrib[(long long)i * P + k] = c;
-        if (is_max) acc = c > acc ? c : acc;
-        else acc = acc + c;
+        if (g_contrib) g_contrib[(long long)i * P + k] = t.c;
+        acc = score_accumulate(acc, t);
     }
     if (domain || divzero) {
         g_status[k] = domain ? FSQ_SCORE_DOMAIN : FSQ_SCORE_DIVZERO;
         return;
     }
     double result;
-    switch (metric) {
-    case FSQ_SCORE_NAIVE:
-    case FSQ_SCORE_MY_CANBERRA:
-    case FSQ_SCORE_MY_CHEBYSHEV:
-    case FSQ_SCORE_MY_STD_NORMALIZED_CHEBYSHEV:
-        result = acc;
-        break;
-    case FSQ_SCORE_MY_NORMALIZED_CHEBYSHEV:
-        if (n_contrib == 0) {
-            g_status[k] = FSQ_SCORE_DOMAIN;
-            return;
-        }
-        result = acc;
-        break;
-    case FSQ_SCORE_LOG_RMSD:
-        result = sqrt(acc / (double)n_contrib);
-        break;
-    default:
-        result = sqrt(acc);
-        break;
+    if (!score_result(metric, acc, n_contrib, &result)) {
+        g_status[k] = FSQ_SCORE_DOMAIN;
+        return;
     }
     g_score[k] = result;
     g_status[k] = FSQ_SCORE_OK;

@@ -23,8 +23,16 @@ NotImplementedError), a point has at most `table_slots` distinct signals (ValueE
 Ten of signal_correlation's metrics are built (METRICS: those whose terms are non-negative sums or maxima); the others raise
 NotImplementedError with the metric's name.  Sums run in ascending key order where the reference's run in dict order: a sum of
 S non-negative terms differs by at most a relative 2 S 2^-53.  best_point's tie rule: the first point in grid order (the
-reference's: its dict order); points without a result (None) are never chosen."""
+reference's: its dict order); points without a result (None) are never chosen.
+
+The rest of match_diagnostic stands at the end of this file: its incompatibility loop over all pairs of heat-map signals
+(:833-889) as fsq_signal_pair_best and fsq_signal_pair_extremes on the same count matrix (incompatibility_device,
+incompatibility_records), the heat-map tables without plotly (single_drops_table, double_drops_table) and match_diagnostic
+itself, which returns what the notebook cell plots."""
 import ctypes
+import decimal
+import itertools
+import math
 
 import numpy as np
 
@@ -306,6 +314,29 @@ def _scores_on_device(table, d_fit, d_fit_total, metric, normalization, small_co
     return out
 
 
+def _counts_on_device(observed_signals, sweep, molecular, device):
+    """(the ordered signals of the observed dict and every point's dict, the count matrix int64 [S, P] and the points' totals
+    int64 [P] as CUDA tensors) of sweep_device's dict (its tables are read where they are) or sweep_records'."""
+    torch = _engine._torch()
+    if "all_simulations" in sweep:
+        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
+        signals = H.ordered_signals(set(observed_signals).union(*dicts))
+        fit, fit_total = H.fit_matrix(signals, dicts)
+        dev = torch.device(device or "cuda")
+        return signals, torch.from_numpy(fit).to(dev), torch.from_numpy(fit_total).to(dev)
+    tables = sweep["molecular" if molecular else "signals"]
+    if tables is None:
+        raise ValueError("the sweep was run with fit=False: pass molecular=True")
+    occupied = torch.unique(tables["keys"][tables["keys"] != NS.EMPTY]).cpu().tolist()
+    signals = H.ordered_signals(set(observed_signals) | {H.signal_of_key(k) for k in occupied})
+    wanted = [H.key_of_signal(s) for s in signals]
+    d_wanted = torch.from_numpy(np.array([NS.NEVER if k is None else k for k in wanted], np.uint64).view(np.int64)).to(tables["keys"].device)
+    d_fit, d_total = lookup_device(tables, d_wanted), tables["counts"].sum(dim=1)
+    if int(d_total.max()) > NS.MAX_COUNT:
+        raise NotImplementedError("counts beyond 2^31 - 1")
+    return signals, d_fit, d_total
+
+
 def score_device(observed_signals, sweep, metric='naive', normalize_counts=False, heatmap_normalize_counts=False,
                  small_count_cutoff=None, contributions=True, molecular=False, device=None, **kw):
     """signal_correlation of observed_signals against every point of a sweep, on the device: a dict of CUDA tensors score and
@@ -313,26 +344,9 @@ def score_device(observed_signals, sweep, metric='naive', normalize_counts=False
     [S, P] (NaN: none) or None, and `signals`, the S signals in the order of the sums.  `sweep` is sweep_device's dict (its
     tables are read where they are) or sweep_records' (its dicts are uploaded as a count matrix); molecular=True scores the
     molecular signals instead of the fitted ones.  The keywords are signal_correlation's."""
-    torch = _engine._torch()
     opts, norm = _score_options(kw), H.normalization_of(normalize_counts, heatmap_normalize_counts)
     H.check_metric(metric)
-    if "all_simulations" in sweep:
-        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
-        signals = H.ordered_signals(set(observed_signals).union(*dicts))
-        fit, fit_total = H.fit_matrix(signals, dicts)
-        dev = torch.device(device or "cuda")
-        d_fit, d_total = torch.from_numpy(fit).to(dev), torch.from_numpy(fit_total).to(dev)
-    else:
-        tables = sweep["molecular" if molecular else "signals"]
-        if tables is None:
-            raise ValueError("the sweep was run with fit=False: pass molecular=True")
-        occupied = torch.unique(tables["keys"][tables["keys"] != NS.EMPTY]).cpu().tolist()
-        signals = H.ordered_signals(set(observed_signals) | {H.signal_of_key(k) for k in occupied})
-        wanted = [H.key_of_signal(s) for s in signals]
-        d_wanted = torch.from_numpy(np.array([NS.NEVER if k is None else k for k in wanted], np.uint64).view(np.int64)).to(tables["keys"].device)
-        d_fit, d_total = lookup_device(tables, d_wanted), tables["counts"].sum(dim=1)
-        if int(d_total.max()) > NS.MAX_COUNT:
-            raise NotImplementedError("counts beyond 2^31 - 1")
+    signals, d_fit, d_total = _counts_on_device(observed_signals, sweep, molecular, device)
     table = H.key_table(observed_signals, signals, **opts)
     return _scores_on_device(table, d_fit, d_total, metric, norm, small_count_cutoff, contributions)
 
@@ -391,3 +405,322 @@ def signal_correlation(observed_signals, fit_signals, heatmap_only=True, zero_on
     return score_records(observed_signals, sweep, metric, normalize_counts, heatmap_normalize_counts, small_count_cutoff, True, False,
                          host, 'raise', device, heatmap_only=heatmap_only, zero_only=zero_only, exclude_signals=exclude_signals,
                          select_signals=select_signals, allow_multidrop=allow_multidrop)[0]
+
+
+# ---- match_diagnostic: the incompatibility scores of signal pairs (jupyter_development.py:786-1259) ----
+
+def split_heatmap(num_cycles, cycle):
+    """jupyter_development.split_heatmap (:227-248): the heat-map signals whose last drop is before `cycle`, and the others,
+    as two tuples; each the single drops ((('A', c),), True, 1) by c, then the double drops ((('A', b), ('A', c)), True, 2) by
+    c, then b."""
+    singles = [((('A', c),), True, 1) for c in range(1, num_cycles + 1)]
+    doubles = [((('A', b), ('A', c)), True, 2) for c in range(1, num_cycles + 1) for b in range(1, c)]
+    last = lambda sig: sig[0][-1][1]                                                   # noqa: E731
+    return (tuple(s for s in singles + doubles if last(s) < cycle), tuple(s for s in singles + doubles if last(s) >= cycle))
+
+
+def py2_round(x):
+    """Python 2's round(x): to the nearest integer, halves away from zero, as a float."""
+    x = float(x)
+    whole = math.floor(abs(x))
+    return math.copysign(whole + (1.0 if abs(x) - whole >= 0.5 else 0.0), x)       # (abs(x) - whole is exact)
+
+
+def py2_round2(x):
+    """Python 2's round(x, 2): the exact value of the float to two decimals, halves away from zero (0.125 -> 0.13, where
+    Python 3 gives 0.12; 2.675, a little below the half, -> 2.67 in both)."""
+    x = float(x)
+    if x != x or x in (float("inf"), float("-inf")):
+        return x
+    return float(decimal.Decimal(x).quantize(decimal.Decimal("0.01"), rounding=decimal.ROUND_HALF_UP))
+
+
+def _candidates(select_signals, num_cycles):
+    if select_signals is None:
+        if num_cycles is None:
+            raise ValueError("num_cycles or select_signals is needed")
+        select_signals = split_heatmap(int(num_cycles), 0)[1]
+    L = list(select_signals)
+    if len(set(L)) != len(L):
+        raise ValueError("a candidate signal stands twice")
+    if not 2 <= len(L) <= H.MAX_SEL:
+        raise ValueError("2 .. %d candidate signals are needed, not %d" % (H.MAX_SEL, len(L)))
+    return L
+
+
+def _candidate_rows(signals, L):
+    index = {s: i for i, s in enumerate(signals)}
+    return np.array([index.get(s, -1) for s in L], np.int32)
+
+
+def pair_best_device(table, rows, d_fit, d_fit_total, metric, normalization=0, small_count_cutoff=None, reverse_order=False):
+    """fsq_signal_pair_best for the candidates whose rows in the key table are `rows` (int32 [n_sel], -1: in no dict), over the
+    count matrix d_fit int64 [S, P] and the totals d_fit_total int64 [P] on the device: a dict of CUDA tensors best_point int32
+    [K], result and factor float64 [K], dist float64 [K, 2], error_point and error_status int32 [K].  Under
+    heatmap_normalize_counts the points' heat-map factor comes from one fsq_signal_scores call with nothing admitted."""
+    torch = _engine._torch()
+    dev = d_fit.device
+    S, P = (int(x) for x in d_fit.shape)
+    rows = np.ascontiguousarray(rows, np.int32)
+    n_sel = int(rows.shape[0])
+    if rows.ndim != 1 or not 2 <= n_sel <= NS.MAX_SEL:
+        raise ValueError("2 .. %d candidate rows are needed" % NS.MAX_SEL)
+    prm = NS.FsqScoreParams()
+    prm.n_observed, prm.metric, prm.normalization = table["n_observed"], H.check_metric(metric), normalization
+    prm.has_cutoff, prm.small_count_cutoff = (0, 0.0) if small_count_cutoff is None else (1, float(small_count_cutoff))
+    heat = None
+    if normalization & NS.HEATMAP_NORMALIZE_COUNTS:
+        heat = _scores_on_device(dict(table, admitted=np.zeros_like(table["admitted"])), d_fit, d_fit_total, H.METRICS[0],
+                                 NS.HEATMAP_NORMALIZE_COUNTS, None, False)
+    d = {k: torch.from_numpy(table[k]).to(dev) for k in ("observed", "in_observed", "admitted")}
+    d_rows = torch.from_numpy(rows).to(dev)
+    K = n_sel * (n_sel - 1) // 2
+    out = {"best_point": torch.empty(K, dtype=torch.int32, device=dev), "result": torch.empty(K, dtype=torch.float64, device=dev),
+           "factor": torch.empty(K, dtype=torch.float64, device=dev), "dist": torch.empty((K, 2), dtype=torch.float64, device=dev),
+           "error_point": torch.empty(K, dtype=torch.int32, device=dev), "error_status": torch.empty(K, dtype=torch.int32, device=dev)}
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None       # noqa: E731
+    _engine.launch(NS.lib().fsq_signal_pair_best, "fsq_signal_pair_best", dev, ptr(d["observed"]), ptr(d["in_observed"]),
+                   ptr(d["admitted"]), ptr(d_fit), d_fit_total.data_ptr(), S, P, ctypes.byref(prm), d_rows.data_ptr(), n_sel,
+                   int(bool(reverse_order)), heat["factor"].data_ptr() if heat else None, heat["status"].data_ptr() if heat else None,
+                   *[out[k].data_ptr() for k in ("best_point", "result", "factor", "dist", "error_point", "error_status")])
+    return out
+
+
+def pair_extremes_device(d_dist, n_sel, reverse_order=False):
+    """fsq_signal_pair_extremes: (score float64 [n_sel], n_distances int32 [n_sel]) of fsq_signal_pair_best's dist."""
+    torch = _engine._torch()
+    n_sel = int(n_sel)
+    if d_dist.dtype != torch.float64 or not d_dist.is_contiguous() or not 2 <= n_sel <= NS.MAX_SEL \
+            or d_dist.numel() != n_sel * (n_sel - 1):
+        raise ValueError("a contiguous float64 tensor [n_sel (n_sel - 1) / 2, 2] is needed, 2 <= n_sel <= %d" % NS.MAX_SEL)
+    score = torch.empty(n_sel, dtype=torch.float64, device=d_dist.device)
+    n = torch.empty(n_sel, dtype=torch.int32, device=d_dist.device)
+    _engine.launch(NS.lib().fsq_signal_pair_extremes, "fsq_signal_pair_extremes", d_dist.device, d_dist.data_ptr(), n_sel,
+                   int(bool(reverse_order)), score.data_ptr(), n.data_ptr())
+    return score, n
+
+
+def incompatibility_device(observed_signals, sweep, select_signals=None, num_cycles=None, metric='naive', normalize_counts=False,
+                           heatmap_normalize_counts=False, small_count_cutoff=None, reverse_order=False, molecular=False,
+                           device=None, **signal_correlation_keywords):
+    """match_diagnostic's incompatibility loop (:833-889) on the device.  For every pair of the candidate signals - select_signals
+    in its order, by default split_heatmap(num_cycles, 0)[1] - and every point of the sweep, signal_correlation with
+    select_signals = the pair; per pair the best point, its result and factor and the two signals' contributions there; per
+    signal the largest of its contributions over its pairs (the smallest with reverse_order), None skipped.  Returns a dict of
+    CUDA tensors - best_point int32 [K] (-1: no point has a result), result, factor float64 [K], dist float64 [K, 2] (NaN:
+    None), error_point, error_status int32 [K], score float64 [n_sel] (NaN: none), n_distances int32 [n_sel] - with `signals`
+    (the candidates) and `points`.  Pairs stand in itertools.combinations' order.  `sweep` is sweep_device's or sweep_records'
+    dict, as for score_device; the other keywords are signal_correlation's."""
+    opts, norm = _score_options(signal_correlation_keywords), H.normalization_of(normalize_counts, heatmap_normalize_counts)
+    if opts.get("select_signals") is not None:
+        raise TypeError("select_signals is the candidate list")
+    H.check_metric(metric)
+    L = _candidates(select_signals, num_cycles)
+    signals, d_fit, d_total = _counts_on_device(observed_signals, sweep, molecular, device)
+    table = H.key_table(observed_signals, signals, **opts)
+    out = pair_best_device(table, _candidate_rows(signals, L), d_fit, d_total, metric, norm, small_count_cutoff, reverse_order)
+    out["score"], out["n_distances"] = pair_extremes_device(out["dist"], len(L), reverse_order)
+    out["signals"], out["points"] = L, list(sweep["points"])
+    return out
+
+
+def incompatibility_records(observed_signals, sweep, select_signals=None, num_cycles=None, metric='naive', normalize_counts=False,
+                            heatmap_normalize_counts=False, small_count_cutoff=None, reverse_order=False, molecular=False,
+                            device=None, host=False, on_error='raise', pairs=True, **signal_correlation_keywords):
+    """incompatibility_device's result in the reference's shapes: {"pairs": {(ss1, ss2): (point, (d1, d2), factor)} - its
+    select_signal_distances (:872); a pair without a best point has (None, (None, None), None) - and "scores": {signal: value} -
+    its max_incompatibilities (:887); a signal without a distance is left out}.  pairs=False leaves "pairs" out (None): at 2 *
+    10^6 pairs the dict is the slow part.  Where a (pair, point) ends in the reference's ZeroDivisionError or ValueError,
+    on_error='raise' raises it, naming the pair and the point, and on_error='none' takes that point as one without a result.
+    host=True: the NumPy twin (sweep_records' dict is then needed)."""
+    if on_error not in ('raise', 'none'):
+        raise ValueError("on_error must be 'raise' or 'none'")
+    if host:
+        opts, norm = _score_options(signal_correlation_keywords), H.normalization_of(normalize_counts, heatmap_normalize_counts)
+        if opts.get("select_signals") is not None:
+            raise TypeError("select_signals is the candidate list")
+        L = _candidates(select_signals, num_cycles)
+        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
+        signals = H.ordered_signals(set(observed_signals).union(*dicts))
+        fit, fit_total = H.fit_matrix(signals, dicts)
+        out = H.pair_best(H.key_table(observed_signals, signals, **opts), _candidate_rows(signals, L), fit, fit_total, metric, norm,
+                          small_count_cutoff, reverse_order)
+        out["score"], out["n_distances"] = H.pair_extremes(out["dist"], len(L), reverse_order)
+        points = list(sweep["points"])
+    else:
+        dev = incompatibility_device(observed_signals, sweep, select_signals, num_cycles, metric, normalize_counts,
+                                     heatmap_normalize_counts, small_count_cutoff, reverse_order, molecular, device,
+                                     **signal_correlation_keywords)
+        L, points = dev["signals"], dev["points"]
+        wanted = ("error_point", "error_status", "score") + (("best_point", "factor", "dist") if pairs else ())
+        out = {k: dev[k].cpu().numpy() for k in wanted}
+    n_sel = len(L)
+    bad = np.flatnonzero(out["error_point"] >= 0)
+    if on_error == 'raise' and len(bad):
+        t = int(bad[0])
+        i, j = next(itertools.islice(itertools.combinations(range(n_sel), 2), t, None))
+        where = " (pair %r, point %r)" % ((L[i], L[j]), points[int(out["error_point"][t])])
+        if int(out["error_status"][t]) == H.SCORE_DIVZERO:
+            raise ZeroDivisionError("float division by zero" + where)
+        raise ValueError("signal_correlation: the maximum of no contributions, or the root of a negative variance" + where)
+    score = out["score"].tolist()
+    result = {"pairs": None, "scores": {s: v for s, v in zip(L, score) if v == v}}
+    if pairs:
+        none = lambda v: v if v == v else None                                     # noqa: E731
+        best, factor, dist = out["best_point"].tolist(), out["factor"].tolist(), out["dist"].tolist()
+        result["pairs"] = {}
+        for t, (i, j) in enumerate(itertools.combinations(range(n_sel), 2)):
+            k = best[t]
+            result["pairs"][(L[i], L[j])] = ((points[k], (none(dist[t][0]), none(dist[t][1])), factor[t]) if k >= 0
+                                             else (None, (None, None), None))
+    return result
+
+
+def _cycles_header(num_mocks, num_edmans, num_mocks_omitted):
+    return (["M" + str(i + 1 + num_mocks_omitted) for i in range(num_mocks - num_mocks_omitted)]
+            + ["E" + str(i + 1) for i in range(num_edmans)])
+
+
+def single_drops_table(signals, num_mocks, num_edmans, num_mocks_omitted, plot_remainders=True, float_data=False):
+    """The heatmap_array of single_drops_heatmap_v2 (:585-620) and its header: (int64 or float64 [1, cycles (+ 1)], the column
+    names M.., E.., R).  Only signals that start at one dye or none count: a drop at cycle c that ends at zero in column c - 1,
+    and with plot_remainders the dye that never drops in the last column.  float_data rounds to two decimals as Python 2
+    does.  A cell written twice with a non-zero first value is the reference's AssertionError."""
+    total_cycles = num_mocks - num_mocks_omitted + num_edmans
+    size = total_cycles + 1 if plot_remainders else total_cycles
+    array = np.zeros((1, size), np.float64 if float_data else np.int64)
+    for (signal, is_zero, starting_intensity), count in signals.items():
+        if starting_intensity > 1 or len(signal) != 1:
+            continue
+        if tuple(signal) == H.NO_DROPS:
+            if not plot_remainders or is_zero:
+                continue
+            y = size - 1
+        elif not is_zero:
+            continue
+        else:
+            y = signal[0][1] - 1
+        assert array[0, y] == 0
+        array[0, y] = py2_round2(count) if float_data else count
+    return array, _cycles_header(num_mocks, num_edmans, num_mocks_omitted) + ["R"]
+
+
+def double_drops_table(signals, num_mocks, num_edmans, num_mocks_omitted, plot_multidrops=False, plot_remainders=True,
+                       float_data=False):
+    """The heatmap_array of double_drops_heatmap_v2 (:674-713) and its headers: (int64 or float64 [cycles, cycles (+ 1)], the
+    column names, the row names).  Only signals that start at two dyes or fewer count: drops at cycles b <= c that end at zero
+    in cell [b - 1, c - 1] (b == c only with plot_multidrops), and with plot_remainders one drop at b that leaves a dye in
+    the last column of row b - 1."""
+    total_cycles = num_mocks - num_mocks_omitted + num_edmans
+    size_x, size_y = total_cycles, total_cycles + 1 if plot_remainders else total_cycles
+    array = np.zeros((size_x, size_y), np.float64 if float_data else np.int64)
+    for (signal, is_zero, starting_intensity), count in signals.items():
+        if starting_intensity > 2:
+            continue
+        if len(signal) == 1:
+            if tuple(signal) == H.NO_DROPS or not plot_remainders or is_zero:
+                continue
+            x, y = signal[0][1] - 1, size_y - 1
+        elif len(signal) == 2:
+            if (not plot_multidrops and len(signal) > len(set(signal))) or not is_zero:
+                continue
+            x, y = signal[0][1] - 1, signal[1][1] - 1
+        else:
+            continue
+        assert array[x, y] == 0
+        array[x, y] = py2_round2(count) if float_data else count
+    rows = _cycles_header(num_mocks, num_edmans, num_mocks_omitted)
+    return array, rows + ["R"] if plot_remainders else list(rows), rows
+
+
+TABLE_NAMES = ("single_observed", "single_fit", "single_diff", "double_observed", "double_fit", "double_diff",
+               "single_contributions", "single_molecular", "single_incompatibility",
+               "double_contributions", "double_molecular", "double_incompatibility")
+
+
+def check_diagnostic_options(normalize_counts, heatmap_normalize_counts, heatmap_only, allow_multidrop, incompatibility_threshold,
+                             compute_incompatibility_scores):
+    """match_diagnostic's three ValueErrors (:806-815)."""
+    if normalize_counts == heatmap_normalize_counts:
+        raise ValueError("normalize_counts == heatmap_normalize_counts")
+    if heatmap_only and (not heatmap_normalize_counts or allow_multidrop):
+        raise ValueError("If heatmap_only, then heatmap_normalize_counts and not allow_multidrop")
+    if incompatibility_threshold is not None and not compute_incompatibility_scores:
+        raise ValueError("If incompatibility_threshold is not None, then compute_incompatibility_scores")
+
+
+def match_diagnostic(all_simulations, observed_signals, metric, reverse_order, normalize_counts, heatmap_normalize_counts,
+                     heatmap_only, zero_only, allow_multidrop, small_count_cutoff, matching_p, split_cycle,
+                     incompatibility_threshold, compute_incompatibility_scores, num_mocks, num_mocks_omitted, num_edmans,
+                     num_cycles=None, apply_exclusion=False, host=False, on_error='raise', device=None):
+    """jupyter_development.match_diagnostic (:786-1259) without its figure, its shelf file and its module-level cache.
+    all_simulations is the reference's {point: (signals, molecular_signals)}, or sweep_records' or sweep_device's dict.  Returns
+    a dict: optimal_pbu, result, normalization_factor and optimal_contributions of the best point (:921-948);
+    normalized_plot_signals and normalized_plot_molecular_signals, its counts scaled to the observed total (:949-953);
+    diff_plot_signals (:956-959); incompatibility_scores ({} when not computed); exclude_signals (:907-916); `tables`, the
+    twelve heat-map arrays of :1005-1190 under TABLE_NAMES, and `z_ranges` (:993-1003; None where the reference's max() would
+    have nothing to take).  reference_tuple() gives the reference's return value.
+
+    Where this differs from the reference, on purpose: the incompatibility loop scores `observed_signals`, not a notebook
+    global (:846); num_cycles=None means num_mocks - num_mocks_omitted + num_edmans, the heat maps' own count (:590-591), not
+    :805's num_mocks + num_mocks_omitted - num_edmans; the exclusion set is returned, and goes into the final scoring only
+    with apply_exclusion=True (the reference prints it and passes None, :928).  As in the reference, allow_multidrop is
+    checked (:808-812) and not passed on to signal_correlation (:845-859, :921-935)."""
+    check_diagnostic_options(normalize_counts, heatmap_normalize_counts, heatmap_only, allow_multidrop, incompatibility_threshold,
+                             compute_incompatibility_scores)
+    sweep = all_simulations if "points" in all_simulations else {"points": list(all_simulations), "all_simulations": all_simulations}
+    records = sweep if "all_simulations" in sweep else records_of_sweep(sweep)
+    if num_cycles is None:
+        num_cycles = num_mocks - num_mocks_omitted + num_edmans
+    kw = dict(metric=metric, normalize_counts=normalize_counts, heatmap_normalize_counts=heatmap_normalize_counts,
+              small_count_cutoff=small_count_cutoff, host=host, on_error=on_error, device=device, heatmap_only=heatmap_only,
+              zero_only=zero_only, matching_p=matching_p)
+    incompatibility_scores = {}
+    if compute_incompatibility_scores:
+        incompatibility_scores = incompatibility_records(observed_signals, records if host else sweep, None, num_cycles,
+                                                         reverse_order=reverse_order, pairs=False, **kw)["scores"]
+    exclude = set()
+    if incompatibility_threshold is not None:
+        exclude = {s for s, mi in incompatibility_scores.items() if mi > incompatibility_threshold}
+    exclude_signals = exclude | set(split_heatmap(num_cycles, split_cycle)[0])
+    scores = score_records(observed_signals, records if host else sweep, exclude_signals=exclude_signals if apply_exclusion else None,
+                           **kw)
+    optimal_pbu, result, factor, contributions = best_point(scores, reverse_order)
+    plot_signals, plot_molecular = records["all_simulations"][optimal_pbu]
+    scaled = lambda d: {s: int(py2_round(n * factor)) for s, n in d.items()}       # noqa: E731
+    normalized, normalized_molecular = scaled(plot_signals), scaled(plot_molecular)
+    diff = {s: float(n - normalized[s]) / n for s, n in observed_signals.items() if s in normalized and n > 0}
+    single, double = [], []
+    for (s, z, si), count in itertools.chain(observed_signals.items(), normalized.items(), normalized_molecular.items()):
+        if not z or len(s) > len(set(s)):
+            continue
+        if len(s) == 1:
+            assert si == 1, "si != 1"
+            single.append(count)
+        elif len(s) == 2:
+            assert si == 2
+            double.append(count)
+        else:
+            assert si > 2, "si <= 2"
+    both = list(incompatibility_scores.values()) + list(contributions.values())
+    z_ranges = {"single_drop": (0, max(single)) if single else None, "double_drop": (0, max(double)) if double else None,
+                "incompatibility": (min(0, min(both)), max(both)) if both else None,
+                "diff": (min(diff.values()), max(diff.values())) if diff else None}
+    shape = (num_mocks, num_edmans, num_mocks_omitted)
+    sources = (observed_signals, normalized, diff, observed_signals, normalized, diff, contributions, normalized_molecular,
+               incompatibility_scores, contributions, normalized_molecular, incompatibility_scores)
+    tables = {}
+    for name, source in zip(TABLE_NAMES, sources):
+        table = single_drops_table if name.startswith("single") else double_drops_table
+        tables[name] = table(source, *shape, plot_remainders=True,
+                             float_data=name.split("_")[1] in ("diff", "contributions", "incompatibility"))[0]
+    return {"optimal_pbu": optimal_pbu, "result": result, "normalization_factor": factor, "optimal_contributions": contributions,
+            "normalized_plot_signals": normalized, "normalized_plot_molecular_signals": normalized_molecular,
+            "diff_plot_signals": diff, "incompatibility_scores": incompatibility_scores, "exclude_signals": exclude_signals,
+            "tables": tables, "z_ranges": z_ranges, "num_cycles": num_cycles,
+            "headers": {"single": single_drops_table({}, *shape)[1], "double": double_drops_table({}, *shape)[1:]}}
+
+
+def reference_tuple(diagnostic):
+    """The reference's return value (:1259) of match_diagnostic's dict."""
+    return (diagnostic["normalized_plot_signals"], diagnostic["optimal_contributions"], diagnostic["incompatibility_scores"])

@@ -11,7 +11,11 @@ is the rate per cycle, as in simulate_peptide.  SIGNALS.pkl holds the observed {
 their defaults.  Writes Sweep_<hash>.pkl, a pickle (protocol 2) of a dict: args, points (the (edman_efficiency,
 dye_destruction, dud_dyes) triples in grid order), all_simulations {point: (signals, molecular_signals)}, total_count,
 none_count, scores {point: (result, (normalization_factor, contributions))} and best_point (point, result,
-normalization_factor, contributions); prints the best point and its score.  --host runs the NumPy twins; no GPU needed."""
+normalization_factor, contributions); prints the best point and its score.  --incompatibility adds `diagnostic`,
+signal_sweep.match_diagnostic's dict (the incompatibility scores of the heat-map signals over all their pairs, the signals
+above --incompatibility_threshold united with those before --split_cycle as exclude_signals, the best point's counts scaled to
+the observed total and the twelve heat-map tables), and prints the number of excluded signals and the five highest scores; it
+needs --heatmap_normalize_counts, or --all_signals with --normalize_counts.  --host runs the NumPy twins; no GPU needed."""
 import argparse
 import itertools
 import os
@@ -76,6 +80,9 @@ def build_parser():
     p.add_argument('--nonzero_signals', action='store_true', default=False, help="Score signals that do not end at zero (zero_only=False).")
     p.add_argument('--score_multidrop', action='store_true', default=False, help="Score signals with repeated drops (allow_multidrop).")
     p.add_argument('--small_count_cutoff', type=float, default=None)
+    p.add_argument('--incompatibility', action='store_true', default=False, help="Add match_diagnostic's dict under 'diagnostic'.")
+    p.add_argument('--incompatibility_threshold', type=float, default=None, help="Signals scoring above it are excluded.")
+    p.add_argument('--split_cycle', type=int, default=0, help="Heat-map signals that end before this cycle are excluded.")
     p.add_argument('--molecule_stride', type=int, default=0, help="0: every point sees the same draws.")
     p.add_argument('--table_slots', type=int, default=1024, help="Distinct signals a point can hold: a power of two.")
     p.add_argument('--chunk_rows', type=int, default=1 << 22)
@@ -96,7 +103,14 @@ def load_observed(path):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.incompatibility:                                     # (before the sweep is run, not after it)
+        try:
+            signal_sweep.check_diagnostic_options(args.normalize_counts, args.heatmap_normalize_counts, not args.all_signals,
+                                                  args.score_multidrop, args.incompatibility_threshold, True)
+        except ValueError as e:
+            parser.error("--incompatibility: " + str(e))
     if args.seed is None:
         args.seed = peptide_simulator.fresh_seed()
     observed = load_observed(args.observed)
@@ -130,6 +144,19 @@ def main(argv=None):
            "none_count": {name[k]: v for k, v in sweep["none_count"].items()},
            "scores": {name[k]: v for k, v in scores.items()}}
     out["best_point"] = signal_sweep.best_point(out["scores"], args.reverse_order)
+    if args.incompatibility:
+        print("Scoring the signal pairs at " + str(datetime.now()))
+        named = {"points": grid, "all_simulations": out["all_simulations"]}
+        out["diagnostic"] = signal_sweep.match_diagnostic(
+            named, observed, args.metric, args.reverse_order, args.normalize_counts, args.heatmap_normalize_counts,
+            not args.all_signals, not args.nonzero_signals, args.score_multidrop, args.small_count_cutoff, 0.10, args.split_cycle,
+            args.incompatibility_threshold, True, args.num_mocks, args.num_mocks_omitted, args.num_edmans, host=args.host,
+            on_error='none', device=args.device)
+        ranked = sorted(out["diagnostic"]["incompatibility_scores"].items(), key=lambda x: x[1], reverse=True)
+        print("Excluded signals: " + str(len(out["diagnostic"]["exclude_signals"])))
+        print("Highest incompatibility scores:")
+        for signal, score in ranked[:5]:
+            print("  " + str(signal) + ": " + repr(score))
     with open(output_filepath, 'wb') as f:
         pickle.dump(out, f, protocol=2)
     point, result, factor, _ = out["best_point"]

@@ -2,8 +2,9 @@
  *
  * jupyter_development.py's loop over all_simulations = {(p, b, u): (signals, molecular_signals)} (match_diagnostic, :786-948)
  * as one device path: a simulation batched over many parameter points, a signal tally per point that stays on the device,
- * and signal_correlation (:279-578) for every point at once.  Conventions are those of fsq_peptide_sim.h: every entry
- * enqueues on `stream` and does not synchronise, buffers are the caller's, return codes are those of include/fsq.h, an
+ * and signal_correlation (:279-578) for every point at once; then match_diagnostic's incompatibility loop over signal pairs
+ * (:833-889) on the same count matrix.  Conventions are those of fsq_peptide_sim.h: every entry
+ * enqueues on `stream` and does not synchronise (but for fsq_signal_pair_best's check of its rows, see there), buffers are the caller's, return codes are those of include/fsq.h, an
  * invalid shape or parameter returns FSQ_EINVAL and writes nothing.
  *
  * THE SIGNAL KEY.  A row of dye counts (a molecule's counts, or a fit's best_seq), uint8 [frames], has the reference's signal
@@ -122,6 +123,48 @@ int fsq_signal_scores(const int64_t* d_observed, const uint8_t* d_in_observed, c
                       const int64_t* d_fit, const int64_t* d_fit_total, int32_t n_keys, int32_t n_points,
                       const FsqScoreParams* prm, double* d_score, double* d_factor, int32_t* d_status, double* d_contrib,
                       void* stream);
+
+/* The complete candidate list of 63 cycles (the key's highest cycle) is 63 single and 63 * 62 / 2 double drops: 2 016 signals
+ * and 2 031 120 pairs.  The cap lies above it, and keeps every pair and distance index within 32 bits. */
+#define FSQ_SIGNAL_PAIR_MAX_SEL 2048
+
+/* match_diagnostic's incompatibility loop (:838-874) for all pairs of n_sel candidate signals at once.  Pair t = (i, j), i < j,
+ * in itertools.combinations' order: t = i (2 n_sel - i - 1) / 2 + j - i - 1, K = n_sel (n_sel - 1) / 2 pairs.  For pair t
+ * and point k the result is what fsq_signal_scores gives at k when d_admitted is ANDed with the two keys d_rows[i] and
+ * d_rows[j] (:845-859, select_signals = {ss1, ss2}): the same pairing, cutoff, factor, terms and statuses.  The best point of
+ * the pair (:861-869) is the one with the smallest result, or the largest with reverse_order != 0; among equal results the
+ * lowest point, and never a point that is not FSQ_SCORE_OK.
+ *   d_observed .. d_fit_total, n_keys, n_points, prm   as fsq_signal_scores takes them
+ *   d_rows         int32 [n_sel]      the row of each candidate in the key table, -1: in no dict (never paired); rows >= 0
+ *                                     are distinct (the caller's to see to: a row standing twice is counted twice)
+ *   d_heat_factor  double [n_points], d_heat_status int32 [n_points]: read when prm->normalization has
+ *                  FSQ_SCORE_HEATMAP_NORMALIZE_COUNTS, else may be null.  The point's heat-map factor does not depend on the
+ *                  pair: it is d_factor and d_status of one fsq_signal_scores call with an all-zero d_admitted (status
+ *                  FSQ_SCORE_EMPTY with the factor, or FSQ_SCORE_DIVZERO).
+ *   d_best_point   int32 [K]          -1: no point has a result
+ *   d_result, d_factor double [K]     at the best point, NaN without one
+ *   d_dist         double [K][2]      the contributions of i and of j at the best point (:871); NaN: none
+ *   d_error_point  int32 [K]          the lowest point that ends FSQ_SCORE_DIVZERO or FSQ_SCORE_DOMAIN (the reference raises
+ *                                     out of its loop there), -1: none;  d_error_status int32 [K]: its status, 0 without one
+ * Every output element is written on every call.  One wavefront per pair, lanes strided over the points; no atomics, no lane
+ * reads another's store, every loop is bounded by n_points.  Needs 2 <= n_sel <= FSQ_SIGNAL_PAIR_MAX_SEL, n_points >= 1,
+ * n_keys >= 0 and every row within -1 .. n_keys - 1 (d_rows is read back to check it: this entry synchronises `stream`
+ * before it launches). */
+int fsq_signal_pair_best(const int64_t* d_observed, const uint8_t* d_in_observed, const uint8_t* d_admitted, const int64_t* d_fit,
+                         const int64_t* d_fit_total, int32_t n_keys, int32_t n_points, const FsqScoreParams* prm,
+                         const int32_t* d_rows, int32_t n_sel, int32_t reverse_order, const double* d_heat_factor,
+                         const int32_t* d_heat_status, int32_t* d_best_point, double* d_result, double* d_factor, double* d_dist,
+                         int32_t* d_error_point, int32_t* d_error_status, void* stream);
+
+/* The per-signal incompatibility score (:875-889): for each of the n_sel candidates the maximum of its distances over its
+ * n_sel - 1 pairs, or the minimum with reverse_order != 0, NaN skipped in both directions.
+ *   d_dist         double [K][2]      fsq_signal_pair_best's
+ *   d_score        double [n_sel]     NaN: the candidate has no distance (the reference leaves it out of its dict)
+ *   d_n_distances  int32  [n_sel]     how many of its n_sel - 1 distances are not NaN
+ * One wavefront per candidate, a fixed reduction tree, no atomics: the same bits on every run.  Needs 2 <= n_sel <=
+ * FSQ_SIGNAL_PAIR_MAX_SEL. */
+int fsq_signal_pair_extremes(const double* d_dist, int32_t n_sel, int32_t reverse_order, double* d_score, int32_t* d_n_distances,
+                             void* stream);
 
 #ifdef __cplusplus
 }
