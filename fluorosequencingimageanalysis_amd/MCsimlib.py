@@ -13,6 +13,12 @@ peptide sample_size times, one lane per sample, into 64-bit signal keys; fsq_pro
 two open-addressing tables that stay on the device; fsq_proteome_uniques scans every signal's proteins as find_uniques does.
 host=True runs the NumPy twins of _host_proteome_mc instead; both give the same integers.  SignalTrie, monte_carlo_trie and
 random_signal are drop-ins built from the records, one Python object per signal: the slow path.
+Shorter runs from the same simulation (:1560-1759): fsq_proteome_project re-tallies the counted pairs under one key mask per
+cycle count - key & mask is the signal a run of c cycles would have shown, which is what SignalTrie.truncating_projection
+leaves in a trie - for many cycle counts in one launch (project_device, projection_records), adds one run into another as
+SignalTrie.merge does (merge_device, merge_records) and feeds the same compaction, sorts and scan for the whole curve of
+identifiable proteins against cycle count (cycle_curve_records; the command line is proteome_cycles).  SignalTrie.graft,
+prune, merge and truncating_projection are host methods of the drop-in; load_proteome (:55-86) reads a proteome pickle.
 
 ORDER CONTRACTS.  (1) Wherever the reference iterates `windows` - a dict, whose order Python 2 leaves open - this module
 iterates sorted(windows); a signal is a tuple sorted by position, then by acid in that order.  (2) Proteins are scanned in
@@ -31,7 +37,8 @@ together, and a head of at most 255 residues; an Edman delay row (one per gap le
 signal_slots <= 2^27 and pair_slots <= 2^28, a table too small for the run raises ValueError naming the keyword.
 
 NOT BUILT: edman_failure_gaps, perfect, window_filter (the enumerating, non-Monte-Carlo route) and the Polyfluor* classes
-(peptide_simulator covers one label's chemistry); each raises NotImplementedError saying so.  discard, truncate_heads and the
+(peptide_simulator covers one label's chemistry); each raises NotImplementedError saying so.  SlimSignalTrie is not there at
+all, and a shorter run is a projection of the long run's draws, not a new photobleaching simulation.  discard, truncate_heads and the
 *_MP / monte_carlo_dictionary functions raise DeprecationWarning, as in the reference."""
 import ctypes
 import random as _random
@@ -142,17 +149,20 @@ def signals_device(dtable, u, sample_size, seed, first_sample=0, first_row=0, n_
     return key, protein, draws
 
 
-def new_tables(signal_slots, pair_slots, device):
+def new_tables(signal_slots, pair_slots, device, n_masks=None):
     """The empty tables of fsq_proteome_tally: signals int64 [signal_slots] (0: free), pairs int64 [pair_slots] (-1: free), counts
-    int64 [pair_slots], overflow int32 [2]."""
+    int64 [pair_slots], overflow int32 [2].  With n_masks, fsq_proteome_project's: each with a leading [n_masks]."""
     torch, NP = _engine()._torch(), _native()
     sa, sb = int(signal_slots), int(pair_slots)
     if sa < 1 or sa & (sa - 1) or sa > NP.MAX_SIGNAL_SLOTS:
         raise ValueError("signal_slots=%d must be a power of two up to 2^27" % sa)
     if sb < 1 or sb & (sb - 1) or sb > NP.MAX_PAIR_SLOTS:
         raise ValueError("pair_slots=%d must be a power of two up to 2^28" % sb)
-    return {"signals": torch.zeros(sa, dtype=torch.int64, device=device), "pairs": torch.full((sb,), -1, dtype=torch.int64, device=device),
-            "counts": torch.zeros(sb, dtype=torch.int64, device=device), "overflow": torch.zeros(2, dtype=torch.int32, device=device)}
+    lead = () if n_masks is None else (int(n_masks),)
+    return {"signals": torch.zeros(lead + (sa,), dtype=torch.int64, device=device),
+            "pairs": torch.full(lead + (sb,), -1, dtype=torch.int64, device=device),
+            "counts": torch.zeros(lead + (sb,), dtype=torch.int64, device=device),
+            "overflow": torch.zeros(lead + (2,), dtype=torch.int32, device=device)}
 
 
 def tally_device(tables, d_key, d_protein):
@@ -305,6 +315,250 @@ def identifiable_proteins(uniq):
     return {uniq["names"][i]: int(n[i]) for i in np.flatnonzero(n).tolist()}
 
 
+# ---- shorter runs: projections, merges and the cycle curve (:1674-1759) ----
+
+def last_position(layout):
+    """The layout's last observable position: a cycle count at or above it changes no signal."""
+    return H.last_position(layout)
+
+
+def _same_space(a, b):
+    if list(a["names"]) != list(b["names"]):
+        raise ValueError("the two runs have different names: their protein indices do not mean the same proteins")
+    if a["layout"].windows != b["layout"].windows:
+        raise ValueError("the two runs have different layouts (windows): their keys do not mean the same signals")
+
+
+def _source_pairs(source, device=None):
+    """The sorted pairs of a run (monte_carlo_device, cycle_tables) or of records on the device: key int64 (bits), protein int32,
+    count int64 and the number of distinct signals."""
+    torch = _engine()._torch()
+    if "tables" in source:
+        if source["tables"]["pairs"].dim() != 1:
+            raise ValueError("the tables of one cycle count are needed: cycle_tables(projection, i)")
+        key, protein, count, segment = pairs_device(source["tables"])
+        return key, protein, count, int(segment.shape[0]) - 1
+    dev = torch.device(device or "cuda")
+    k = np.ascontiguousarray(source["key"], np.uint64)
+    key = torch.from_numpy(k.view(np.int64)).to(dev)
+    protein = torch.from_numpy(np.ascontiguousarray(source["protein"], np.int32)).to(dev)
+    count = torch.from_numpy(np.ascontiguousarray(source["count"], np.int64)).to(dev)
+    return key, protein, count, len(np.unique(k))
+
+
+def project_into(tables, d_key, d_protein, d_count, d_mask, mode=H.PROJECT):
+    """fsq_proteome_project: the counted pairs (int64 key bits [n], int32 [n], int64 [n] or None for weight 1) under the masks
+    d_mask (int64 bits [n_masks]) into `tables` - new_tables(..., n_masks=n_masks), or one table where n_masks is 1.  Enqueued,
+    not synchronised."""
+    torch, NP = _engine()._torch(), _native()
+    n, n_masks = int(d_key.shape[0]), int(d_mask.shape[0])
+    if d_key.dtype != torch.int64 or d_protein.dtype != torch.int32 or d_key.dim() != 1 or tuple(d_protein.shape) != (n,):
+        raise ValueError("int64 keys [n] and int32 proteins [n] are needed")
+    if d_count is not None and (d_count.dtype != torch.int64 or tuple(d_count.shape) != (n,)):
+        raise ValueError("int64 counts [n] are needed")
+    if d_mask.dtype != torch.int64 or d_mask.dim() != 1:
+        raise ValueError("int64 masks [n_masks] are needed")
+    if not all(t is None or t.is_contiguous() for t in (d_key, d_protein, d_count, d_mask) + tuple(tables.values())):
+        raise ValueError("contiguous tensors are needed")
+    sa, sb = int(tables["signals"].shape[-1]), int(tables["pairs"].shape[-1])
+    if (tables["signals"].numel(), tables["pairs"].numel(), tables["counts"].numel(), tables["overflow"].numel()) != \
+            (n_masks * sa, n_masks * sb, n_masks * sb, n_masks * 2):
+        raise ValueError("the tables do not hold %d masks" % n_masks)
+    _engine().launch(NP.lib().fsq_proteome_project, "fsq_proteome_project", d_key.device, d_key.data_ptr() if n else None,
+                     d_protein.data_ptr() if n else None, d_count.data_ptr() if n and d_count is not None else None, n,
+                     d_mask.data_ptr(), n_masks, int(mode), tables["signals"].data_ptr(), sa, tables["pairs"].data_ptr(),
+                     tables["counts"].data_ptr(), sb, tables["overflow"].data_ptr())
+
+
+def cycle_tables(projection, i):
+    """The tables of the i-th cycle count of a project_device result, in the form of new_tables: pairs_device reads them,
+    tally_device and project_into go on adding to them.  With names and layout, so that it serves where a run does."""
+    return {"tables": {k: v[i] for k, v in projection["tables"].items()}, "names": projection["names"], "layout": projection["layout"]}
+
+
+def check_projection(projection):
+    """Raises ValueError for the first cycle count whose tables were too small."""
+    t = projection["tables"]
+    for i, (a, b) in enumerate(t["overflow"].cpu().tolist()):
+        if a:
+            raise ValueError("more distinct signals than signal_slots=%d at cycles=%d: pass a larger power of two"
+                             % (int(t["signals"].shape[-1]), projection["cycles"][i]))
+        if b:
+            raise ValueError("more distinct (signal, protein) pairs than pair_slots=%d at cycles=%d: pass a larger power of two"
+                             % (int(t["pairs"].shape[-1]), projection["cycles"][i]))
+
+
+def project_device(run_or_records, cycles, mode="project", signal_slots=None, pair_slots=None, masks_per_launch=None, device=None,
+                   mask_major=False):
+    """The tally of a run (monte_carlo_device, cycle_tables) or of records under every cycle count of `cycles`, on the device:
+    mode 'project' folds every signal onto what a run of c cycles would have shown (truncating_projection, :1697-1759), 'within'
+    keeps the signals whose last position is at most c (merge's cycles=, :1694).  Returns a dict: `tables` (new_tables with
+    n_masks=len(cycles): row i is the tally of cycles[i]; see cycle_tables), `cycles`, `masks`, `names`, `layout`, `mode`.
+    signal_slots / pair_slots are powers of two; by default the power of two at or above twice the source's distinct signals and
+    twice its pairs, which a projection cannot exceed.  At most masks_per_launch cycle counts go into one launch (None: all; the
+    entry takes 4 096), which bounds a launch's items, not the tables: they are held for every cycle count asked for.  The result
+    does not depend on it, nor on mask_major (the item order of the kernel, there to be timed).  A table that is too small raises
+    ValueError naming its keyword and the cycle count."""
+    torch, NP = _engine()._torch(), _native()
+    which = H.mode_of(mode) | (NP.MASK_MAJOR if mask_major else 0)
+    layout = run_or_records["layout"]
+    masks = H.cycle_masks(layout, cycles)
+    cycles = [int(c) for c in cycles]
+    if not cycles:
+        raise ValueError("no cycle count")
+    per = len(cycles) if masks_per_launch is None else int(masks_per_launch)
+    if per < 1:
+        raise ValueError("masks_per_launch must be positive")
+    per = min(per, NP.MAX_MASKS)
+    key, protein, count, n_signals = _source_pairs(run_or_records, device)
+    tables = new_tables(_pow2_at_least(2 * n_signals) if signal_slots is None else signal_slots,
+                        _pow2_at_least(2 * int(key.shape[0])) if pair_slots is None else pair_slots, key.device, n_masks=len(cycles))
+    d_mask = torch.from_numpy(masks.view(np.int64)).to(key.device)
+    for lo in range(0, len(cycles), per):
+        project_into({k: v[lo:lo + per] for k, v in tables.items()}, key, protein, count, d_mask[lo:lo + per], which)
+    out = {"tables": tables, "cycles": cycles, "masks": masks, "names": list(run_or_records["names"]), "layout": layout, "mode": mode}
+    check_projection(out)
+    return out
+
+
+def _records(triples, source):
+    k, p, c = triples
+    return {"key": k, "protein": p, "count": c, "names": list(source["names"]), "layout": source["layout"]}
+
+
+def _records_of_tables(run):
+    key, protein, count, _ = pairs_device(run["tables"])
+    return _records((key.cpu().numpy().view(np.uint64), protein.cpu().numpy(), count.cpu().numpy()), run)
+
+
+def projection_records(source, cycles, host=False, mode="project", device=None):
+    """The records of `source` (records, or a run on the device) as a run of `cycles` Edman cycles would have given them, in the
+    shape of monte_carlo_records: uniques_records, uniques_dict and trie_of_records take them unchanged."""
+    if host:
+        if "tables" in source:
+            raise ValueError("host=True needs records, not a device result")
+        mask = H.cycle_masks(source["layout"], [cycles])[0]
+        return _records(H.project((source["key"], source["protein"], source["count"]), mask, mode), source)
+    return _records_of_tables(cycle_tables(project_device(source, [cycles], mode, device=device), 0))
+
+
+def merge_device(run_a, run_b, cycles=None):
+    """SignalTrie.merge (:1674-1696) on the device: adds the pairs of run_b - with cycles, those whose last position is at most
+    cycles - into run_a's tables, and returns run_a.  A table of run_a that is too small raises ValueError naming its keyword."""
+    torch = _engine()._torch()
+    _same_space(run_a, run_b)
+    key, protein, count, _ = _source_pairs(run_b, run_a["tables"]["pairs"].device)
+    mask = np.array([H.ALL_ONES], np.uint64) if cycles is None else H.cycle_masks(run_a["layout"], [cycles])
+    project_into(run_a["tables"], key, protein, count, torch.from_numpy(mask.view(np.int64)).to(key.device),
+                 H.PROJECT if cycles is None else H.WITHIN)
+    check_tables(run_a["tables"])
+    if "rows" in run_a and "rows" in run_b:
+        run_a["rows"] += run_b["rows"]
+    return run_a
+
+
+def merge_records(a, b, cycles=None, host=False, device=None):
+    """The records of a plus those of b (with cycles: those of b whose last position is at most cycles), as merge leaves a trie."""
+    _same_space(a, b)
+    if host:
+        mask = None if cycles is None else H.cycle_masks(a["layout"], [cycles])[0]
+        return _records(H.merge(*[(r["key"], r["protein"], r["count"]) for r in (a, b)], mask=mask), a)
+    torch = _engine()._torch()
+    key, protein, count, n_signals = _source_pairs(a, device)
+    tables = new_tables(_pow2_at_least(2 * (n_signals + len(np.unique(b["key"])))), _pow2_at_least(2 * (len(a["key"]) + len(b["key"]))),
+                        key.device)
+    project_into(tables, key, protein, count, torch.full((1,), -1, dtype=torch.int64, device=key.device))
+    run = {"tables": tables, "names": list(a["names"]), "layout": a["layout"]}
+    return _records_of_tables(merge_device(run, b, cycles))
+
+
+def _sorted_projection(projection):
+    """Every cycle count's occupied pairs in one pass, sorted by (cycle index, key as uint64, protein): cycle int64, key int64
+    (bits), protein int32, count int64 and segment int64 [signals + 1] over all cycle counts."""
+    torch = _engine()._torch()
+    t = projection["tables"]
+    occupied = t["pairs"] != -1
+    cyc = occupied.nonzero(as_tuple=True)[0]
+    pair, count = t["pairs"][occupied], t["counts"][occupied]
+    key, protein = t["signals"][cyc, pair >> 32], pair & 0xffffffff
+    order = torch.sort(protein, stable=True)[1]
+    order = order[torch.sort((key ^ (-1 << 63))[order], stable=True)[1]]
+    order = order[torch.sort(cyc[order], stable=True)[1]]
+    cyc, key, protein, count = cyc[order], key[order].contiguous(), protein[order].to(torch.int32).contiguous(), count[order].contiguous()
+    n = int(key.shape[0])
+    new = torch.ones(n, dtype=torch.bool, device=key.device)
+    if n > 1:
+        new[1:] = (key[1:] != key[:-1]) | (cyc[1:] != cyc[:-1])
+    segment = torch.cat([new.nonzero().reshape(-1), torch.tensor([n], dtype=torch.int64, device=key.device)]).contiguous()
+    return cyc, key, protein, count, segment
+
+
+def cycle_curve_records(source, worst_ratio, absolute_min, maximum_secondary=None, cycles=None, absolute=False, demote=False,
+                        host=False, device=None):
+    """Identifiable proteins against the number of Edman cycles, from one simulation: find_uniques' scan (absolute=True:
+    find_uniques_absolute's, absolute_min its minimum_best) of `source` (records, or a run on the device) projected onto every
+    cycle count of `cycles` (None: 1 .. the layout's last observable position).  Proteins are scanned in ascending index (order
+    contract (2)).  Returns int64 arrays over the cycle counts - cycles, n_signals, n_pairs, samples_detected (the sum of counts),
+    n_passing_signals, n_identifiable_proteins - with identifiable uint8 [len(cycles)][n_proteins] (1: best for a passing signal)
+    and names.  The long run's draws are kept, as the reference's projection keeps them; the curve need not be monotone.
+    On the device all cycle counts go through one projection launch, one compaction, three sorts and one fsq_proteome_uniques
+    launch over the concatenated segments."""
+    layout, names = source["layout"], list(source["names"])
+    if cycles is None:
+        cycles = range(1, H.last_position(layout) + 1)
+    cycles = [int(c) for c in cycles]
+    H.cycle_masks(layout, cycles)
+    if not cycles:
+        raise ValueError("no cycle count: the layout has no observable position")
+    modes = H.scan_modes(None if absolute else worst_ratio, absolute_min, maximum_secondary, absolute=absolute)
+    if host:
+        if "tables" in source:
+            raise ValueError("host=True needs records, not a device result")
+        out = H.cycle_curve((source["key"], source["protein"], source["count"]), layout, len(names), cycles, modes, demote)
+        out["names"] = names
+        return out
+    torch = _engine()._torch()
+    C, P = len(cycles), len(names)
+    cyc, _, protein, count, segment = _sorted_projection(project_device(source, cycles, device=device))
+    got = uniques_device(protein, count, segment, modes, demote)
+    dev = cyc.device
+    of_signal = cyc[segment[:-1]]
+    passed = got["passed"] != 0
+    zeros = lambda: torch.zeros(C, dtype=torch.int64, device=dev)               # noqa: E731
+    identifiable = torch.zeros(C * max(P, 1), dtype=torch.uint8, device=dev)
+    identifiable[(of_signal * max(P, 1) + got["best_protein"].to(torch.int64))[passed]] = 1
+    identifiable = identifiable.reshape(C, max(P, 1))[:, :P]
+    out = {"cycles": np.array(cycles, np.int64), "n_signals": torch.bincount(of_signal, minlength=C),
+           "n_pairs": torch.bincount(cyc, minlength=C), "samples_detected": zeros().index_add_(0, cyc, count),
+           "n_passing_signals": zeros().index_add_(0, of_signal, passed.to(torch.int64)),
+           "n_identifiable_proteins": identifiable.sum(dim=1, dtype=torch.int64), "identifiable": identifiable.contiguous()}
+    out = {k: v if isinstance(v, np.ndarray) else v.cpu().numpy() for k, v in out.items()}
+    out["names"] = names
+    return out
+
+
+def load_proteome(filename, silent=True):
+    """:55-86: a pickle of {protein name: amino-acid sequence}.  Python 2's text pickles are read with encoding='latin1'."""
+    import pickle
+    import time
+    t0 = time.perf_counter()
+    if not silent:
+        print("")
+        print("unpickling proteome from " + str(filename))
+    try:
+        with open(filename, 'rb') as f:
+            proteome = pickle.load(f, encoding="latin1")
+    except Exception:
+        print("Proteome unpickling error.")
+        raise
+    if not isinstance(proteome, dict) or not all(isinstance(k, str) and isinstance(v, str) for k, v in proteome.items()):
+        raise ValueError("%s does not hold a dict of {name: sequence} strings" % filename)
+    if not silent:
+        print("proteome loaded in " + str(time.perf_counter() - t0) + " sec")
+        print("...")
+    return proteome
+
+
 # ---- drop-ins ----
 
 class SignalTrie(object):
@@ -372,6 +626,76 @@ class SignalTrie(object):
             else:
                 used += 1
         return empty, used
+
+    def graft(self, signal, signal_count):
+        """:1630-1673: adds signal_count = {protein: count} to `signal`'s node, made if it is not there.  Returns self."""
+        assert len(signal) > 0
+        assert signal[0] == self.signal_block or self.signal_block == (None, None), \
+            ('signal: ' + str(signal) + '; self.signal_block: ' + str(self.signal_block))
+        assert len(signal_count) > 0
+        if self.signal_block == (None, None):
+            self.descendants.setdefault(signal[0], SignalTrie(signal[0])).graft(signal, signal_count)
+        elif len(signal) == 1:
+            for protein in signal_count:
+                self.signal_count[protein] = self.signal_count.get(protein, 0) + signal_count[protein]
+        else:
+            self.descendants.setdefault(signal[1], SignalTrie(signal[1])).graft(signal[1:], signal_count)
+        return self
+
+    def _detach(self, block):
+        """The counts of the descendant `block`, which leaves the trie if nothing hangs below it and is emptied otherwise."""
+        child = self.descendants[block]
+        if len(child.descendants) == 0:
+            return self.descendants.pop(block).signal_count
+        counts, child.signal_count = child.signal_count, {}
+        return counts
+
+    def prune(self, signal):
+        """:1560-1629: takes `signal` out of the trie and returns (signal, its signal_count).  Called on the root."""
+        assert len(signal) > 0
+        root = self.signal_block == (None, None)
+        if len(signal) == 1:
+            assert root
+            return (signal, self._detach(signal[0]))
+        if root:
+            assert signal[0] in self.descendants
+            return self.descendants[signal[0]].prune(signal)
+        assert signal[0] == self.signal_block, ('self.signal_block ' + str(self.signal_block) + '; signal ' + str(signal))
+        assert signal[1] in self.descendants
+        if len(signal) == 2:
+            return (signal, self._detach(signal[1]))
+        rest = self.descendants[signal[1]].prune(signal[1:])
+        return ((self.signal_block,) + rest[0], rest[1])
+
+    def merge(self, trie, cycles=None):
+        """:1674-1696: grafts every leaf of `trie` (with cycles: those whose last position is at most cycles) onto this root."""
+        assert self.signal_block == (None, None), 'merge can only be called on the root node'
+        for signal, signal_count, _ in list(trie.leaf_iterator()):
+            if cycles is None or signal[-1][0] <= cycles:
+                self.graft(signal, signal_count)
+        return self
+
+    def _has_leaf(self):
+        return next(self.leaf_iterator(), None) is not None
+
+    def truncating_projection(self, cycles):
+        """:1697-1759: folds every signal onto what `cycles` Edman cycles would have shown, in place.  Returns self.  (The root's
+        block position is None, which Python 2 orders below every number: the root counts as within `cycles`.)"""
+        for signal, signal_count, _ in list(self.leaf_iterator()):
+            if signal[-1][0] > cycles:
+                projected = tuple(block for block in signal if block[0] <= cycles)
+                if projected:
+                    self.graft(projected, signal_count)
+        beyond = [(node, block) for signal, _, node in self.node_iterator() for block in node.descendants
+                  if (signal[-1][0] is None or signal[-1][0] <= cycles) and block[0] > cycles]
+        for node, block in beyond:
+            del node.descendants[block]
+        bare = [(node, block) for _, _, node in self.leaf_iterator() for block, child in node.descendants.items()
+                if not child._has_leaf()]
+        bare += [(self, block) for block, child in self.descendants.items() if not child._has_leaf()]
+        for node, block in bare:
+            del node.descendants[block]
+        return self
 
     def _find(self, modes):
         out = {}

@@ -570,3 +570,77 @@ def unique_dict(result, triples, layout, names, demote=False):
     name = lambda i: None if i < 0 else names[i]
     return {signal_of(triples[0][result["segment"][i]], layout): [(name(b[0]), b[1]), [(name(q), c) for q, c in listed], tertiary]
             for i, (b, listed, tertiary) in unique_lists(result, triples, demote).items()}
+
+
+# ---- shorter runs (:1674-1759) ----
+
+PROJECT, WITHIN = 0, 1                      # FSQ_PMC_PROJECT, FSQ_PMC_WITHIN
+MODES = {"project": PROJECT, "within": WITHIN}
+ALL_ONES = (1 << 64) - 1
+
+
+def last_position(layout):
+    """The last observable position of a layout (0: none): no signal changes under a cycle count at or above it."""
+    return max([o.bit_length() - 1 for o in layout.O if o] + [0])
+
+
+def cycle_masks(layout, cycles):
+    """uint64 [len(cycles)]: the key bits of the pairs (x, acid) with x <= c - per acid, bits base_a .. base_a +
+    popcount(O_a & ((1 << (c + 1)) - 1)) - 1.  key & mask is the signal a run of c Edman cycles would have shown
+    (truncating_projection, :1697-1759); c = 0 gives 0, c at or above the last position every bit of the layout."""
+    out = []
+    for c in cycles:
+        if int(c) != c or c < 0:
+            raise ValueError("a cycle count is a non-negative integer (got %r)" % (c,))
+        c, mask = min(int(c), 63), 0
+        for a in range(len(layout.order)):
+            mask |= ((1 << bin(layout.O[a] & ((1 << (c + 1)) - 1)).count("1")) - 1) << layout.base[a]
+        out.append(mask)
+    return np.array(out, np.uint64)
+
+
+def mode_of(mode):
+    if mode not in MODES:
+        raise ValueError("mode is 'project' or 'within' (got %r)" % (mode,))
+    return MODES[mode]
+
+
+def project(triples, mask, mode="project"):
+    """Sorted (key, protein, count) triples under one mask: 'project' re-tallies key & mask (truncating_projection), 'within'
+    keeps the triples with key & ~mask == 0 (merge's cycles= filter, :1694).  Empty keys, negative proteins and zero counts are
+    counted nowhere.  Sorted triples as tally returns them."""
+    which = mode_of(mode)
+    k, p, c = np.asarray(triples[0], np.uint64), np.asarray(triples[1], np.int32), np.asarray(triples[2], np.int64)
+    mask = np.uint64(int(mask))
+    k = np.where((k & ~mask) == 0, k, np.uint64(0)) if which == WITHIN else k & mask
+    keep = (k != 0) & (p >= 0) & (c != 0)
+    empty = (np.zeros(0, np.uint64), np.zeros(0, np.int32), np.zeros(0, np.int64))
+    if not keep.any():
+        return empty
+    return merge_triples((k[keep], p[keep], c[keep]), empty)
+
+
+def merge(a, b, mask=None):
+    """SignalTrie.merge (:1674-1696) on triples: a plus the triples of b within `mask` (None: all of b)."""
+    return merge_triples(project(a, ALL_ONES), project(b, ALL_ONES if mask is None else mask, "project" if mask is None else "within"))
+
+
+CURVE_FIELDS = ("n_signals", "n_pairs", "samples_detected", "n_passing_signals", "n_identifiable_proteins")
+
+
+def cycle_curve(triples, layout, n_proteins, cycles, modes, demote=False):
+    """The scan of find_uniques under every cycle count of `cycles`: a dict of int64 arrays over the cycle counts - cycles,
+    n_signals, n_pairs, samples_detected (the sum of counts), n_passing_signals, n_identifiable_proteins - and identifiable
+    uint8 [len(cycles)][n_proteins], 1 where the protein is best for a passing signal.  `modes` is scan_modes' tuple."""
+    cycles = [int(c) for c in cycles]
+    out = {name: np.zeros(len(cycles), np.int64) for name in CURVE_FIELDS}
+    out["cycles"] = np.array(cycles, np.int64)
+    out["identifiable"] = np.zeros((len(cycles), int(n_proteins)), np.uint8)
+    for i, mask in enumerate(cycle_masks(layout, cycles).tolist()):
+        t = project(triples, mask)
+        u = _uniques(t, modes, demote)
+        out["n_signals"][i], out["n_pairs"][i], out["samples_detected"][i] = len(u["key"]), len(t[0]), t[2].sum()
+        out["n_passing_signals"][i] = np.count_nonzero(u["passed"])
+        out["identifiable"][i, u["best_protein"][u["passed"] != 0]] = 1
+    out["n_identifiable_proteins"] = out["identifiable"].sum(axis=1).astype(np.int64)
+    return out

@@ -14,6 +14,8 @@ MAX_SIGNAL_SLOTS = 1 << 27          # FSQ_PMC_MAX_SIGNAL_SLOTS
 MAX_PAIR_SLOTS = 1 << 28            # FSQ_PMC_MAX_PAIR_SLOTS
 BLOCK, MAX_BLOCKS = 256, 2048       # kpm_signals' and kpm_tally's grid: one pass covers BLOCK * MAX_BLOCKS rows
 RATIO_NONE, RATIO_NUMBER, RATIO_ABSENT = 0, 1, 2        # FSQ_PMC_RATIO_*
+PROJECT, WITHIN, MASK_MAJOR = 0, 1, 0x100               # FSQ_PMC_PROJECT, FSQ_PMC_WITHIN, FSQ_PMC_MASK_MAJOR
+MAX_MASKS = 4096                    # FSQ_PMC_MAX_MASKS
 
 
 class FsqProteomeParams(ctypes.Structure):
@@ -35,6 +37,7 @@ _SIGS = {
     "fsq_proteome_signals": (ctypes.c_int, [ctypes.POINTER(FsqProteomeParams), _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64, _P, _P, _P,
                                             _P]),
     "fsq_proteome_tally": (ctypes.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P]),
+    "fsq_proteome_project": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, ctypes.c_int32, _P, _I64, _P, _P, _I64, _P, _P]),
     "fsq_proteome_uniques": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(FsqUniquesParams), _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTED = tuple(_SIGS)

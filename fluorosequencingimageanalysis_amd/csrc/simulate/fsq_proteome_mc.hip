@@ -5,7 +5,8 @@
 //                 delay is a binary search in the host-built row of running _dp sums, the bleach a binary search in the
 //                 host-built survival table: no exp, no pow, no per-lane arrays.  A peptide's labels are read straight from
 //                 the CSR table: the lanes of a wavefront mostly share a peptide, so these are broadcast loads.
-//   kpm_tally     one lane per (key, protein) row: table A key -> slot, table B (slot, protein) -> count.
+//   kpm_tally     one lane per (key, protein) row: table A key -> slot, table B (slot, protein) -> count (the insert of
+//                 fsq_pmc_insert.h, which fsq_proteome_project.hip shares).
 //   kpm_uniques   one lane per signal: the scan of find_uniques (:1436-1474) over its proteins in ascending index.
 // Every loop has a bound that does not depend on another lane: labels <= 64, a table search <= 13 steps, a probe sequence <=
 // the table's size, a scan = the signal's proteins.  A full table costs counts (and sets d_overflow), never a wait.
@@ -13,18 +14,12 @@
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_proteome_mc.h"
 #include "fsq_philox.h"
+#include "fsq_pmc_insert.h"
 
 namespace {
 
 constexpr int PMC_BLOCK = 256;
 constexpr int PMC_MAX_BLOCKS = 2048;            // one pass of kpm_signals / kpm_tally covers 524 288 rows
-
-__device__ __forceinline__ unsigned long long pmc_hash(unsigned long long x)        // splitmix64's finaliser
-{
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 // the draws of one item's stream 3, random access; the last block is kept
 struct ItemDraws {
@@ -159,27 +154,9 @@ kpm_tally(const unsigned long long* __restrict__ g_key, const int32_t* __restric
         const unsigned long long key = g_key[t];
         const int protein = g_row_protein[t];
         if (key == 0ull || protein < 0) continue;
-        long long slot = -1;
-        const unsigned long long h = pmc_hash(key);
-        for (long long i = 0; i < signal_slots; ++i) {
-            const long long at = (long long)((h + (unsigned long long)i) & (unsigned long long)(signal_slots - 1));
-            const unsigned long long was = atomicCAS(&g_signals[at], 0ull, key);
-            if (was == 0ull || was == key) { slot = at; break; }
-        }
-        if (slot < 0) { g_overflow[0] = 1; continue; }
-        const unsigned long long pair = ((unsigned long long)slot << 32) | (unsigned long long)(uint32_t)protein;
-        const unsigned long long h2 = pmc_hash(pair);
-        bool done = false;
-        for (long long i = 0; i < pair_slots; ++i) {
-            const long long at = (long long)((h2 + (unsigned long long)i) & (unsigned long long)(pair_slots - 1));
-            const unsigned long long was = atomicCAS(&g_pairs[at], (unsigned long long)FSQ_PMC_PAIR_EMPTY, pair);
-            if (was == FSQ_PMC_PAIR_EMPTY || was == pair) {
-                atomicAdd((unsigned long long*)&g_counts[at], 1ull);
-                done = true;
-                break;
-            }
-        }
-        if (!done) g_overflow[1] = 1;
+        const int r = pmc_insert<false>(key, protein, 1ull, g_signals, signal_slots, g_pairs, g_counts, pair_slots);
+        if (r == FSQ_PMC_NO_SIGNAL_SLOT) g_overflow[0] = 1;
+        else if (r == FSQ_PMC_NO_PAIR_SLOT) g_overflow[1] = 1;
     }
 }
 

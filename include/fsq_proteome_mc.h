@@ -3,7 +3,9 @@
  * The reference's MCsimlib.py samples every attached peptide of a proteome sample_size times with random_signal (:863-1074),
  * counts the signals per source protein in a SignalTrie (:1224-1281) and asks find_uniques (:1398-1486) which signals point
  * to one protein.  Here that is three entries on the device: the signals as 64-bit keys, the (signal, protein) counts in two
- * open-addressing tables, and the scan of find_uniques over the sorted counts.  Conventions are those of
+ * open-addressing tables, and the scan of find_uniques over the sorted counts.  A fourth, fsq_proteome_project, folds a
+ * tally onto what shorter runs would have shown (truncating_projection, :1697-1759) for many cycle counts at once, and adds one
+ * tally into another (merge, :1674-1696).  Conventions are those of
  * fsq_signal_sweep.h: every entry enqueues on `stream` and does not synchronise, buffers are the caller's, return codes are
  * those of include/fsq.h, an invalid shape or parameter returns FSQ_EINVAL and writes nothing.
  *
@@ -83,7 +85,30 @@ int fsq_proteome_tally(const uint64_t* d_key, const int32_t* d_row_protein, int6
                        int64_t signal_slots, uint64_t* d_pairs, int64_t* d_counts, int64_t pair_slots, int32_t* d_overflow,
                        void* stream);
 
-#define FSQ_PMC_RATIO_NONE 0                /* worst_ratio is None: passes only without a second */
+#define FSQ_PMC_PROJECT 0                   /* insert key & mask: truncating_projection (:1697-1759) */
+#define FSQ_PMC_WITHIN 1                    /* insert key where key & ~mask == 0: merge's cycles= filter (:1694) */
+#define FSQ_PMC_MASK_MAJOR 0x100            /* or-ed into the mode: item t is pair t % n under mask t / n, not pair t / n_masks under
+                                               mask t % n_masks.  The tables do not depend on it; it is there to be timed */
+#define FSQ_PMC_MAX_MASKS 4096
+
+/* The counted pairs (d_key[i], d_protein[i], d_count[i]) under each of n_masks masks, one lane per (pair, mask) item: table m of
+ * [n_masks][signal_slots] / [n_masks][pair_slots] receives the pair's key as `mode` and d_mask[m] turn it.  The mask of cycle
+ * count c holds the key bits of the pairs (x, a) with x <= c: per acid, bits base_a .. base_a + popcount(O_a & ((1 << (c + 1))
+ * - 1)) - 1, so key & mask is the signal a run of c cycles would have shown.
+ *   d_key uint64 [n], d_protein int32 [n], d_count int64 [n] or null (every weight 1), d_mask uint64 [n_masks]
+ *   d_signals uint64 [n_masks][signal_slots], d_pairs uint64 [n_masks][pair_slots], d_counts int64 [n_masks][pair_slots],
+ *   d_overflow int32 [n_masks][2]
+ * Table m has the slot format of fsq_proteome_tally and is prepared as there; calls accumulate, and fsq_proteome_tally may go on
+ * adding to it.  An item whose turned key is 0, whose protein is negative or whose weight is 0 is counted nowhere.  The count
+ * is one 64-bit integer atomic add of the weight; probe loops are bounded by the table's size; a full table sets
+ * d_overflow[m][0] (signals) or [m][1] (pairs), loses that item and leaves the other masks exact.  Null pointers (d_count
+ * aside), n_masks outside 1 .. FSQ_PMC_MAX_MASKS, slot counts that are no power of two within the limits above or an unknown
+ * mode return FSQ_EINVAL and write nothing; n == 0 returns FSQ_OK. */
+int fsq_proteome_project(const uint64_t* d_key, const int32_t* d_protein, const int64_t* d_count, int64_t n, const uint64_t* d_mask,
+                         int64_t n_masks, int32_t mode, uint64_t* d_signals, int64_t signal_slots, uint64_t* d_pairs,
+                         int64_t* d_counts, int64_t pair_slots, int32_t* d_overflow, void* stream);
+
+#define FSQ_PMC_RATIO_NONE 0               /* worst_ratio is None: passes only without a second */
 #define FSQ_PMC_RATIO_NUMBER 1
 #define FSQ_PMC_RATIO_ABSENT 2              /* find_uniques_absolute: no ratio clause, second_count <= maximum_secondary */
 
