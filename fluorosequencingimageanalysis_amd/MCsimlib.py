@@ -37,7 +37,7 @@ together, and a head of at most 255 residues; an Edman delay row (one per gap le
 signal_slots <= 2^27 and pair_slots <= 2^28, a table too small for the run raises ValueError naming the keyword.
 
 NOT BUILT: edman_failure_gaps, perfect, window_filter (the enumerating, non-Monte-Carlo route) and the Polyfluor* classes
-(peptide_simulator covers one label's chemistry); each raises NotImplementedError saying so.  SlimSignalTrie is not there at
+(peptide_simulator covers the chemistry, for several label letters too: multilabel_records); each raises NotImplementedError saying so.  SlimSignalTrie is not there at
 all, and a shorter run is a projection of the long run's draws, not a new photobleaching simulation.  discard, truncate_heads and the
 *_MP / monte_carlo_dictionary functions raise DeprecationWarning, as in the reference."""
 import ctypes
@@ -63,10 +63,10 @@ def _not_built(name, why):
 edman_failure_gaps = _not_built("edman_failure_gaps", "the enumerating route is out of scope; use monte_carlo_records")
 perfect = _not_built("perfect", "the enumerating route is out of scope (and perfect raises DeprecationWarning in the reference)")
 window_filter = _not_built("window_filter", "random_signal already applies the windows")
-PolyfluorSignal = _not_built("PolyfluorSignal", "peptide_simulator covers one label's chemistry")
-PolyfluorSignalTrie = _not_built("PolyfluorSignalTrie", "peptide_simulator covers one label's chemistry")
-PolyfluorPeptide = _not_built("PolyfluorPeptide", "peptide_simulator covers one label's chemistry")
-PolyfluorPeptide_v2 = _not_built("PolyfluorPeptide_v2", "peptide_simulator covers one label's chemistry")
+PolyfluorSignal = _not_built("PolyfluorSignal", "peptide_simulator covers the chemistry (several label letters: multilabel_records)")
+PolyfluorSignalTrie = _not_built("PolyfluorSignalTrie", "peptide_simulator covers the chemistry (several label letters: multilabel_records)")
+PolyfluorPeptide = _not_built("PolyfluorPeptide", "peptide_simulator covers the chemistry (several label letters: multilabel_records)")
+PolyfluorPeptide_v2 = _not_built("PolyfluorPeptide_v2", "peptide_simulator covers the chemistry (several label letters: multilabel_records)")
 
 
 def _engine():

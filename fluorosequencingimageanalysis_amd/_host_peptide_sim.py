@@ -8,6 +8,13 @@ and key (seed & 0xffffffff, seed >> 32); even j takes words (0, 1), odd j words 
 ((a >> 5) * 67108864 + (b >> 6)) / 2**53.  Stream 0: the chemistry (random.random() of simulate_dye_counts); stream 1: the
 superdye draws; stream 2: the uniforms behind the normals.
 
+Several label letters, one colour channel each (include/fsq_peptide_labels.h, `simulate_labels`).  Draw contract: stream 0
+is the chemistry on the union of the channels' positions, in the same order - the reference draws once per residue whose
+letter is in `labels`, whatever the letter; channel 0's photometry reads streams 1 and 2, channel k >= 1 streams 2 + 2k
+(superdyes) and 3 + 2k (normals) - stream 3 is the proteome Monte-Carlo's; every channel of every molecule starts with an
+empty Gaussian cache.  With one channel every table is `simulate`'s.  Order contract: the reference iterates a Python-2
+dict of letters; the channels here are the sorted label letters, and a channel's draws do not depend on that order.
+
 Also the engine of `python -m fluorosequencingimageanalysis_amd.simulate_peptide --host`."""
 import math
 
@@ -17,7 +24,7 @@ M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 MASK32 = 0xffffffff
 CAUSE_NONE, CAUSE_DUD, CAUSE_DESTRUCTION, CAUSE_EDMAN, CAUSE_STRIP = 0, 1, 2, 3, 4
 CAUSE_NAMES = {CAUSE_DUD: 'dye dud', CAUSE_DESTRUCTION: 'dye destruction', CAUSE_EDMAN: 'edman', CAUSE_STRIP: 'surface strip'}
-MAX_FRAMES, MAX_LENGTH, MAX_LABELLED = 64, 64, 15
+MAX_FRAMES, MAX_LENGTH, MAX_LABELLED, MAX_CHANNELS = 64, 64, 15, 4
 OFF_LOG = -10000.0
 
 KNOWN_ANSWERS = (
@@ -143,8 +150,9 @@ def max_chemistry_draws(n_labelled, num_mocks, num_edmans):
     return 2 * n_labelled + num_mocks * (1 + n_labelled) + num_edmans * (2 + n_labelled)
 
 
-def walk(pos, length, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, rnd):
-    """The chemistry of one molecule on the stream-0 draws `rnd`: (counts, loss_cycle, loss_cause, edman_fail)."""
+def walk(pos, length, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, rnd, tap=None):
+    """The chemistry of one molecule on the stream-0 draws `rnd`: (counts, loss_cycle, loss_cause, edman_fail).  tap(live), if
+    given, sees the live flags of the labelled positions after every cycle (simulate_labels counts its channels there)."""
     L = len(pos)
     live = [True] * L
     loss_cycle, loss_cause = [0] * L, [CAUSE_NONE] * L
@@ -155,6 +163,8 @@ def walk(pos, length, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, rnd):
         if live[k] and rnd() > per_cycle_b:
             live[k], loss_cycle[k], loss_cause[k] = False, 0, CAUSE_DESTRUCTION
     counts, nterm, fail = [sum(live)], 0, 0
+    if tap is not None:
+        tap(live)
     for c in range(1, num_mocks + num_edmans + 1):
         if c > num_mocks and nterm < length:                        # Edman (:47-75): draws only while residues remain
             if rnd() < p:
@@ -172,6 +182,8 @@ def walk(pos, length, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, rnd):
             if live[k] and rnd() > per_cycle_b:
                 live[k], loss_cycle[k], loss_cause[k] = False, c, CAUSE_DESTRUCTION
         counts.append(sum(live))
+        if tap is not None:
+            tap(live)
     return counts, loss_cycle, loss_cause, fail
 
 
@@ -231,4 +243,87 @@ def simulate(length, label_mask, num_mocks, num_edmans, p, per_cycle_b, u, s, sc
         out["log_intensity"][i] = [math.log(x) if x > 0 else OFF_LOG for x in inten]
         out["category"][i] = sum(1 << f for f, c in enumerate(counts) if c)
         out["n_draws"][i] = (r0.j, r1.j, r2.j)
+    return out
+
+
+def superdye_stream(k):
+    """The stream of channel k's superdye draws."""
+    return 1 if k == 0 else 2 + 2 * k
+
+
+def normal_stream(k):
+    """The stream of the uniforms behind channel k's normals."""
+    return 2 if k == 0 else 3 + 2 * k
+
+
+def check_channels(length, channel_masks, num_mocks, num_edmans, ddif):
+    """(union positions, the channel of each, frames) after the checks fsq_peptide_simulate_labels makes."""
+    K = len(channel_masks)
+    if not 1 <= K <= MAX_CHANNELS:
+        raise ValueError("1 .. %d channels" % MAX_CHANNELS)
+    if len(ddif) != K:
+        raise ValueError("one ddif row per channel")
+    union, F = 0, None
+    for k, mask in enumerate(channel_masks):
+        if mask & union:
+            raise ValueError("a residue in two channels")
+        union |= mask
+        _, F = check_shape(length, mask, num_mocks, num_edmans, ddif[k])
+    pos = [i for i in range(length) if (union >> i) & 1]
+    return pos, [next(k for k, m in enumerate(channel_masks) if (m >> i) & 1) for i in pos], F
+
+
+def counts_from_losses(channel_of, loss_cycle, loss_cause, K, frames):
+    """The count rows [K][frames] the loss tables of one molecule imply: a dye is there at frame f iff its cause is none or
+    its loss cycle is greater than f."""
+    return [[sum(1 for j, ch in enumerate(channel_of) if ch == k and (loss_cause[j] == CAUSE_NONE or loss_cycle[j] > f))
+             for f in range(frames)] for k in range(K)]
+
+
+def simulate_labels(length, channel_masks, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, log_beta, beta_sigma, ddif,
+                    superdye_rate, superdye_factor, seed=0, first_molecule=0, n_molecules=1):
+    """The records of fsq_peptide_simulate_labels as NumPy arrays, K = len(channel_masks) and L the labelled residues of the
+    union: counts uint8 [K, n, frames], loss_cycle / loss_cause uint8 [n, L], edman_fail uint64 [n], intensity and log_intensity
+    float64 [K, n, frames], category uint64 [K, n], n_draws int32 [n, 1 + 2K].  log_beta, beta_sigma, ddif, superdye_rate and
+    superdye_factor are sequences over the channels."""
+    channel_masks = [int(m) for m in channel_masks]
+    K = len(channel_masks)
+    pos, channel_of, F = check_channels(length, channel_masks, num_mocks, num_edmans, ddif)
+    if not (len(log_beta) == len(beta_sigma) == len(superdye_rate) == len(superdye_factor) == K):
+        raise ValueError("one value per channel")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in 0 .. 2^64 - 1")
+    if not all(0 <= r <= 1 for r in superdye_rate):
+        raise ValueError("superdye_rate must be between 0 and 1 (inclusive).")
+    n, L = int(n_molecules), len(pos)
+    if n < 0 or first_molecule < 0 or first_molecule + n > 1 << 63:
+        raise ValueError("molecule ids must be in 0 .. 2^63 - 1")
+    ddif = [[float(x) for x in row] for row in ddif]
+    mols = [first_molecule + i for i in range(n)]
+    u0 = uniforms_np(seed, mols, 0, max_chemistry_draws(L, num_mocks, num_edmans)).tolist()
+    per = [bin(m).count("1") for m in channel_masks]
+    u1 = [uniforms_np(seed, mols, superdye_stream(k), per[k]).tolist() for k in range(K)]
+    u2 = [uniforms_np(seed, mols, normal_stream(k), 2 * F + 8).tolist() if per[k] else [()] * n for k in range(K)]
+    out = {"counts": np.zeros((K, n, F), np.uint8), "loss_cycle": np.zeros((n, L), np.uint8), "loss_cause": np.zeros((n, L), np.uint8),
+           "edman_fail": np.zeros(n, np.uint64), "intensity": np.zeros((K, n, F)), "log_intensity": np.full((K, n, F), OFF_LOG),
+           "category": np.zeros((K, n), np.uint64), "n_draws": np.zeros((n, 1 + 2 * K), np.int32)}
+    for i, mol in enumerate(mols):
+        r0 = Stream(seed, mol, 0, u0[i])
+        rows = [[] for _ in range(K)]
+
+        def tap(live):
+            for k in range(K):
+                rows[k].append(sum(1 for j, on in enumerate(live) if on and channel_of[j] == k))
+        _, lc, cause, fail = walk(pos, length, num_mocks, num_edmans, p, per_cycle_b, u, s, sc, s2, r0, tap)
+        out["loss_cycle"][i], out["loss_cause"][i], out["edman_fail"][i] = lc, cause, fail
+        out["n_draws"][i, 0] = r0.j
+        for k in range(K):
+            r1 = Stream(seed, mol, superdye_stream(k), u1[k][i])
+            r2 = Stream(seed, mol, normal_stream(k), u2[k][i])
+            inten = photometries(rows[k], log_beta[k], beta_sigma[k], ddif[k], superdye_rate[k], superdye_factor[k], r1, Normals(r2))
+            out["counts"][k, i] = rows[k]
+            out["intensity"][k, i] = inten
+            out["log_intensity"][k, i] = [math.log(x) if x > 0 else OFF_LOG for x in inten]
+            out["category"][k, i] = sum(1 << f for f, c in enumerate(rows[k]) if c)
+            out["n_draws"][i, 1 + 2 * k:3 + 2 * k] = (r1.j, r2.j)
     return out

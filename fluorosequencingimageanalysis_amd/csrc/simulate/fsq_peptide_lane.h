@@ -48,14 +48,15 @@ struct LaneChem {
     double p, per_cycle_b, u, s, s2;
 };
 
-// The chemistry (stream 0): dud and photobleach at cycle 0, then per cycle [Edman,] strip, photobleach.  my_cnt[0 .. C] gets
-// the count of every frame; with LOSS, my_lcyc / my_lcau get the loss cycle and cause of every labelled residue and *fail
-// the cycles whose Edman drew and failed.  Returns the draws consumed.
-template <bool LOSS>
-__device__ __forceinline__ int lane_chemistry(const LaneChem& ch, const unsigned long long seed, const unsigned long long molecule,
-                                              const unsigned long long labels, const int L, const int length, const int num_mocks,
-                                              const int C, const int sc, uint8_t* const my_cnt, uint8_t* const my_lcyc,
-                                              uint8_t* const my_lcau, unsigned long long* const fail)
+// The chemistry (stream 0): dud and photobleach at cycle 0, then per cycle [Edman,] strip, photobleach.  put(c, live) gets
+// the mask of live dyes after every cycle c in 0 .. C; with LOSS, my_lcyc / my_lcau get the loss cycle and cause of every
+// labelled residue and *fail the cycles whose Edman drew and failed.  Returns the draws consumed.  `labels` may be the
+// union of several letters' masks (fsq_peptide_labels.hip): the reference draws per labelled residue whatever its letter.
+template <bool LOSS, class Put>
+__device__ __forceinline__ int lane_chemistry_put(const LaneChem& ch, const unsigned long long seed, const unsigned long long molecule,
+                                                  const unsigned long long labels, const int L, const int length, const int num_mocks,
+                                                  const int C, const int sc, const Put put, uint8_t* const my_lcyc,
+                                                  uint8_t* const my_lcau, unsigned long long* const fail)
 {
     Draws d0 = draws_of(seed, molecule, 0u);
     unsigned long long live = labels;
@@ -85,25 +86,43 @@ __device__ __forceinline__ int lane_chemistry(const LaneChem& ch, const unsigned
             for (unsigned long long m = live; m; m &= m - 1ull) lose(__builtin_ctzll(m), c, FSQ_PEPTIDE_CAUSE_STRIP);
         for (unsigned long long m = live; m; m &= m - 1ull)                     // photobleach (:84-99)
             if (d0.next() > ch.per_cycle_b) lose(__builtin_ctzll(m), c, FSQ_PEPTIDE_CAUSE_DESTRUCTION);
-        my_cnt[c] = (uint8_t)__builtin_popcountll(live);
+        put(c, live);
     }
     return d0.j;
 }
 
-// The photometry of the count row my_cnt[0 .. F): the superdye draws (stream 1) as a bit mask - the suffix sums of :350-352
-// are then popcounts - and per frame with dyes one polar normal (stream 2), the mean summed left to right with glibc's
-// log, glibc's exp.  my_dbl[0 .. F) gets the intensities, 0.0 where the count is 0; returns the category word; *n1 and
-// *n2 get the draws consumed of streams 1 and 2.
-__device__ __forceinline__ unsigned long long lane_photometry(const FsqPeptideSimParams& prm, const double* const s_ddif,
-                                                              const unsigned long long molecule, const int F,
-                                                              const uint8_t* const my_cnt, double* const my_dbl, int* const n1,
-                                                              int* const n2)
+// one label letter: my_cnt[0 .. C] gets the count of every frame
+template <bool LOSS>
+__device__ __forceinline__ int lane_chemistry(const LaneChem& ch, const unsigned long long seed, const unsigned long long molecule,
+                                              const unsigned long long labels, const int L, const int length, const int num_mocks,
+                                              const int C, const int sc, uint8_t* const my_cnt, uint8_t* const my_lcyc,
+                                              uint8_t* const my_lcau, unsigned long long* const fail)
 {
-    Draws d1 = draws_of(prm.seed, molecule, 1u), d2 = draws_of(prm.seed, molecule, 2u);
+    return lane_chemistry_put<LOSS>(ch, seed, molecule, labels, L, length, num_mocks, C, sc,
+                                    [&](int c, unsigned long long live) { my_cnt[c] = (uint8_t)__builtin_popcountll(live); }, my_lcyc,
+                                    my_lcau, fail);
+}
+
+// what the photometry of one colour channel needs beside its ddif row
+struct LanePhot {
+    double log_beta, beta_sigma, superdye_rate, superdye_factor;
+};
+
+// The photometry of the count row my_cnt[0 .. F): the superdye draws (stream s1) as a bit mask - the suffix sums of :350-352
+// are then popcounts - and per frame with dyes one polar normal (stream s2), the mean summed left to right with glibc's
+// log, glibc's exp.  my_dbl[0 .. F) gets the intensities, 0.0 where the count is 0; returns the category word; *n1 and
+// *n2 get the draws consumed of the two streams.  The Gaussian cache starts empty.
+__device__ __forceinline__ unsigned long long lane_photometry_streams(const LanePhot& ph, const unsigned long long seed,
+                                                                      const uint32_t s1, const uint32_t s2, const double* const s_ddif,
+                                                                      const unsigned long long molecule, const int F,
+                                                                      const uint8_t* const my_cnt, double* const my_dbl, int* const n1,
+                                                                      int* const n2)
+{
+    Draws d1 = draws_of(seed, molecule, s1), d2 = draws_of(seed, molecule, s2);
     const int c0 = my_cnt[0];
     unsigned super = 0u;                                                        // bit q: superdye draw q came out true
     for (int q = 0; q < c0; ++q)
-        if (d1.next() < prm.superdye_rate) super |= 1u << q;
+        if (d1.next() < ph.superdye_rate) super |= 1u << q;
     const int total = __builtin_popcount(super);
     unsigned long long category = 0ull;
     bool has_gauss = false;
@@ -114,25 +133,25 @@ __device__ __forceinline__ unsigned long long lane_photometry(const FsqPeptideSi
         double intensity = 0.0;
         if (c > 0) {
             double dyes = (double)c;
-            if (prm.superdye_rate != 0.0) {
+            if (ph.superdye_rate != 0.0) {
                 // the draws of the drops before frame f are the first c0 - counts[f - 1]: what is left of `total`
                 // is the suffix sum of :350-352
                 const int before = f == 0 ? 0 : c0 - prev;
                 const int inc = total - __builtin_popcount(super & ((1u << before) - 1u));
-                dyes = dyes + (double)inc * prm.superdye_factor;
+                dyes = dyes + (double)inc * ph.superdye_factor;
             }
-            const double mean = (prm.log_beta + ln_log(dyes)) - s_ddif[c - 1];
+            const double mean = (ph.log_beta + ln_log(dyes)) - s_ddif[c - 1];
             double z;
             if (has_gauss) {
                 z = gauss;
                 has_gauss = false;
             } else {                                                            // numpy's legacy_gauss
                 int block = d2.j >> 1;
-                z = polar_pair(&block, d2.mlo, d2.mhi, 2u, d2.k0, d2.k1, &gauss);
+                z = polar_pair(&block, d2.mlo, d2.mhi, s2, d2.k0, d2.k1, &gauss);
                 d2.j = 2 * block;
                 has_gauss = true;
             }
-            intensity = fsq_exp(mean + prm.beta_sigma * z);
+            intensity = fsq_exp(mean + ph.beta_sigma * z);
             category |= 1ull << f;
         }
         prev = c;
@@ -140,6 +159,16 @@ __device__ __forceinline__ unsigned long long lane_photometry(const FsqPeptideSi
     }
     *n1 = d1.j; *n2 = d2.j;
     return category;
+}
+
+// one label letter: streams 1 and 2
+__device__ __forceinline__ unsigned long long lane_photometry(const FsqPeptideSimParams& prm, const double* const s_ddif,
+                                                              const unsigned long long molecule, const int F,
+                                                              const uint8_t* const my_cnt, double* const my_dbl, int* const n1,
+                                                              int* const n2)
+{
+    const LanePhot ph = {prm.log_beta, prm.beta_sigma, prm.superdye_rate, prm.superdye_factor};
+    return lane_photometry_streams(ph, prm.seed, 1u, 2u, s_ddif, molecule, F, my_cnt, my_dbl, n1, n2);
 }
 
 inline bool is_finite(double x) { return x - x == 0.0; }

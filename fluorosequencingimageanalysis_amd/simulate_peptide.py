@@ -7,7 +7,12 @@ Writes Simulated_<hash>.pkl, a pickle (protocol 0) of (args, signals, molecular_
 lognormal fitter recovered and the molecular ground truth, and Simulated_<hash>.csv with the simulated photometries unless
 --no_csv.  Every option of the reference's parser is taken with its default; --distance_ddifs is accepted and has no effect
 (the reference passes it on under a name nothing reads) and -n is accepted and unused.  New: --seed (default: a fresh one;
-printed, and stored in the pickled args) makes a run repeatable, --host runs the NumPy twin of the kernels instead of the GPU."""
+printed, and stored in the pickled args) makes a run repeatable, --host runs the NumPy twin of the kernels instead of the GPU.
+
+LABELS may name up to 4 letters, one colour channel each (the reference's command line stops at one, :249).  Every option
+then holds for all letters; the CSV has the channels ch1, ch2, ... in sorted-letter order (a channel's tracks are the molecules
+with a dye of that letter at some frame; a channel without tracks is left out), and the pickle is (args, {letter: signals},
+molecular_error_signals) with the joint keys of peptide_simulator.joint_signal."""
 import argparse
 import os
 import pickle
@@ -26,7 +31,7 @@ MAX_DEVIATION = 3                   # (:283)
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('sequence', nargs=1, type=str, help="The peptide as a string of amino acids.")
-    p.add_argument('labels', nargs=1, type=str, help="The labelled amino acid (one letter).")
+    p.add_argument('labels', nargs=1, type=str, help="The labelled amino acids: 1 .. 4 letters, one colour channel each.")
     p.add_argument('-N', '--num_sims', type=int, default=100000, help="Number of molecules to simulate.")
     p.add_argument('-m', '--num_mocks', type=int, default=4, help="Number of mocks performed.")
     p.add_argument('-o', '--num_mocks_omitted', type=int, default=1, help="Number of mocks not imaged.")
@@ -74,11 +79,23 @@ def molecular_error_signals_of_records(records, kept):
     return _tracks.tally_signals((_tracks.decrements_of_row(counts[i]), counts[i][-1] == 0, counts[i][0]) for i in kept)[0]
 
 
-def host_fit(photometries, beta, beta_sigma, max_possible, allow_multidrop, max_deviation, quench_factors):
+def photometries_of_labels_records(records):
+    """photometries_of_records for several letters: channel 'ch<k + 1>' holds the molecules with a dye of the k-th sorted
+    letter at some frame, track t its t-th such molecule; a channel without tracks is left out."""
+    photometries = {}
+    for k in range(len(records["labels"])):
+        one = {key: records[key][k] for key in ("category", "counts", "intensity")}
+        fdict = photometries_of_records(one)[0]['ch1'][0]
+        if fdict:
+            photometries['ch%d' % (k + 1)] = {0: fdict}
+    return photometries
+
+
+def host_fit(photometries, beta, beta_sigma, max_possible, allow_multidrop, max_deviation, quench_factors, channel='ch1'):
     """(signals, total_count, none_count) of lognormal.photometries_lognormal_fit with the Python restatement of the fit
-    (_host_lognormal.py)."""
+    (_host_lognormal.py), for one channel of the dict."""
     means = _tracks.log_fluor_means(beta, quench_factors, max_possible)
-    tracks = photometries['ch1'][0].values()
+    tracks = photometries[channel][0].values() if channel in photometries else ()
     fits = [_host_lognormal.intensities_to_signal(list(intensities), beta_sigma, max_possible, allow_multidrop, max_deviation,
                                                   category, means) for category, intensities, _ in tracks]
     signals, none_count = _tracks.tally_signals((f[0], f[1], f[6]) for f in fits)
@@ -115,7 +132,26 @@ def main(argv=None):
             print("Failed to write simulated photometries to " + str(csv_filepath) + " due to exception " + str(e))
             traceback.print_exc()
 
-    if args.host:
+    if len(set(labels)) > 1:                                    # several letters, one colour channel each
+        fit_kw = dict(max_possible=MAX_POSSIBLE, allow_multidrop=allow_multidrop, max_deviation=MAX_DEVIATION, quench_factors=ddif)
+        if args.host:
+            records = peptide_simulator.multilabel_records(*shape, seed=args.seed, host=True, **ep)
+            molecular_error_signals = peptide_simulator.joint_signals_of_records(records)
+        else:
+            out = peptide_simulator.multilabel_and_fit_records(*shape, seed=args.seed, device=args.device, **fit_kw, **ep)
+            molecular_error_signals = out["molecular_error_signals"]
+            records = {k: out["simulation"][k].cpu().numpy() for k in ("category", "counts", "intensity")}
+            records["labels"] = out["simulation"]["labels"]
+        photometries = photometries_of_labels_records(records)
+        if not args.no_csv and photometries:
+            write_csv(photometries)
+        print("Simulation complete. Fitting simulated tracks at " + str(datetime.now()))
+        if args.host:
+            signals = {letter: host_fit(photometries, args.fluor_intensity, args.beta_sigma, MAX_POSSIBLE, allow_multidrop,
+                                        MAX_DEVIATION, ddif, 'ch%d' % (k + 1))[0] for k, letter in enumerate(records["labels"])}
+        else:
+            signals = {letter: out[letter]["signals"] for letter in records["labels"]}
+    elif args.host:
         records = peptide_simulator.simulation_records(*shape, seed=args.seed, host=True, **ep)
         photometries, kept = photometries_of_records(records)
         molecular_error_signals = molecular_error_signals_of_records(records, kept)
