@@ -99,12 +99,166 @@ def tally_rows(rows, points, valid, n_points):
     return tables, none, unkeyed
 
 
+# ---- the joint key of several colour channels (include/fsq_signal_sweep.h, THE JOINT KEY) ----
+
+MAX_CHANNELS = 4
+JOINT_DROP_BITS = {1: 6, 2: 7, 3: 8, 4: 8}      # B(K) = 6 + ceil(log2 K)
+JOINT_MAX_DROPS = {1: 10, 2: 8, 3: 6, 4: 6}     # D(K)
+
+
+def _start_shift(K, k):
+    return 0 if k == 0 else 64 - 4 * (K - k)
+
+
+def joint_key_of(starts, drops):
+    """The joint key of K starting counts 0 .. 15 (K = 1 .. 4 channels, in sorted-letter order) and up to D(K) drops (cycle
+    1 .. 63, channel) in ascending order.  With K = 1 it is key_of(starts[0], cycles)."""
+    K = len(starts)
+    B = JOINT_DROP_BITS[K]
+    key = 0
+    for k, start in enumerate(starts):
+        key |= int(start) << _start_shift(K, k)
+    for i, (c, k) in enumerate(drops):
+        key |= (int(c) | int(k) << 6) << (4 + B * i)
+    return key
+
+
+def joint_key_of_signal(letters, signal):
+    """The joint key of peptide_simulator.joint_signal's (decrements, zeros, starts) under the sorted `letters`, or None where
+    no rows have that signal or it has no key: a letter outside `letters`, drops that do not ascend by (cycle, letter) within
+    cycles 1 .. 63, more than D(K) drops in all or more of a letter than its start, a start outside 0 .. 15, a `zeros` entry
+    that is not (the letter's drops == its start)."""
+    try:
+        dec, zeros, starts = signal
+        letters, dec, zeros, starts = tuple(letters), tuple(dec), tuple(zeros), tuple(starts)
+        K = len(letters)
+        if not 1 <= K <= MAX_CHANNELS or len(zeros) != K or len(starts) != K or len(dec) > JOINT_MAX_DROPS[K]:
+            return None
+        if any(int(s) != s or not 0 <= s <= 15 for s in starts) or any(not isinstance(z, (bool, np.bool_)) for z in zeros):
+            return None
+        drops = []
+        for a, c in dec:
+            if a not in letters or int(c) != c or not 1 <= c < MAX_FRAMES:
+                return None
+            drops.append((int(c), letters.index(a)))
+        if any(a > b for a, b in zip(drops, drops[1:])):
+            return None
+        for k in range(K):
+            n = sum(1 for _, ch in drops if ch == k)
+            if n > starts[k] or bool(zeros[k]) != (n == starts[k]):
+                return None
+    except (TypeError, ValueError):
+        return None
+    return joint_key_of(starts, drops)
+
+
+def joint_signal_of_key(letters, key):
+    """(decrements, zeros, starts) of a joint key under the sorted `letters`: what peptide_simulator.joint_signal gives for
+    its rows.  ValueError for a bit pattern that is no molecule's key (EMPTY and NEVER among them)."""
+    key = int(key) & 0xffffffffffffffff                         # (a key read from an int64 tensor may come signed)
+    letters = tuple(letters)
+    K = len(letters)
+    B, D = JOINT_DROP_BITS[K], JOINT_MAX_DROPS[K]
+    starts = [(key >> _start_shift(K, k)) & 15 for k in range(K)]
+    drops, ended = [], False
+    for i in range(D):
+        field = (key >> (4 + B * i)) & ((1 << B) - 1)
+        c, k = field & 63, field >> 6
+        if field == 0:
+            ended = True
+        elif ended or c == 0 or k >= K:
+            raise ValueError("0x%x is not a joint signal key of %d channels" % (key, K))
+        else:
+            drops.append((c, k))
+    spare = (key >> (4 + B * D)) & ((1 << (60 - 4 * (K - 1) - B * D)) - 1)              # the bits between drops and top nibbles
+    n = [sum(1 for _, ch in drops if ch == k) for k in range(K)]
+    if spare or any(a > b for a, b in zip(drops, drops[1:])) or any(n[k] > starts[k] for k in range(K)):
+        raise ValueError("0x%x is not a joint signal key of %d channels" % (key, K))
+    return tuple((letters[k], c) for c, k in drops), tuple(n[k] == starts[k] for k in range(K)), tuple(starts)
+
+
+def joint_signals_of_keys(letters, keys):
+    """[joint_signal_of_key(letters, k) for k in keys] for keys a tally has made (they are not checked), the bit fields taken
+    apart in NumPy: a table of 10^5 .. 10^6 occupied slots becomes its dict in seconds."""
+    letters = tuple(letters)
+    K = len(letters)
+    B, D = JOINT_DROP_BITS[K], JOINT_MAX_DROPS[K]
+    keys = np.ascontiguousarray(keys).view(np.uint64).reshape(-1)
+    starts = np.stack([(keys >> np.uint64(_start_shift(K, k))) & np.uint64(15) for k in range(K)], axis=1).astype(np.int64)
+    fields = np.stack([(keys >> np.uint64(4 + B * i)) & np.uint64((1 << B) - 1) for i in range(D)], axis=1).astype(np.int64)
+    present = fields != 0
+    per_channel = np.stack([(present & (fields >> 6 == k)).sum(axis=1) for k in range(K)], axis=1)
+    pair = [(letters[f >> 6], f & 63) if f >> 6 < K else None for f in range(1 << B)]
+    return [(tuple(pair[f] for f in row[:d]), tuple(z), tuple(st))
+            for row, d, z, st in zip(fields.tolist(), present.sum(axis=1).tolist(), (per_channel == starts).tolist(), starts.tolist())]
+
+
+def classify_joint_rows(rows):
+    """(ROW_SIGNAL, key), (ROW_NONE, None) for a molecule with an upstep in any channel or (ROW_UNKEYED, None) for one with
+    more than D(K) drops in all or a channel that starts above 15, of one molecule's K count rows [K][frames]: kss_tally_joint's
+    joint_row_key."""
+    rows = [[int(c) for c in row] for row in rows]
+    K = len(rows)
+    if not 1 <= K <= MAX_CHANNELS:
+        raise ValueError("a molecule has 1 .. %d channels" % MAX_CHANNELS)
+    if not 1 <= len(rows[0]) <= MAX_FRAMES or any(len(row) != len(rows[0]) for row in rows):
+        raise ValueError("a row has 1 .. %d frames" % MAX_FRAMES)
+    if any(b > a for row in rows for a, b in zip(row, row[1:])):
+        return ROW_NONE, None
+    drops = [(f, k) for f in range(1, len(rows[0])) for k in range(K) for _ in range(rows[k][f - 1] - rows[k][f])]
+    if any(row[0] > 15 for row in rows) or len(drops) > JOINT_MAX_DROPS[K]:
+        return ROW_UNKEYED, None
+    return ROW_SIGNAL, joint_key_of([row[0] for row in rows], drops)
+
+
+def tally_joint_rows(rows, points, valid, n_points):
+    """fsq_signal_tally_joint on the host, rows uint8 [K][n][frames]: ([{key: count}] per point, none [n_points], unkeyed
+    [n_points])."""
+    tables = [{} for _ in range(n_points)]
+    none, unkeyed = [0] * n_points, [0] * n_points
+    rows = np.asarray(rows, dtype=np.uint8)
+    K, n, F = rows.shape
+    flat = np.ascontiguousarray(rows.transpose(1, 0, 2)).reshape(n, K * F)
+    uniq, inverse = np.unique(flat, axis=0, return_inverse=True) if n else (flat, np.zeros(0, np.int64))
+    kinds = [classify_joint_rows(np.reshape(r, (K, F)).tolist()) for r in uniq]
+    for i, u in enumerate(np.asarray(inverse).reshape(-1).tolist()):
+        k = int(points[i])
+        if (valid is not None and not valid[i]) or not 0 <= k < n_points:
+            continue
+        what, key = kinds[u]
+        if what == ROW_SIGNAL:
+            tables[k][key] = tables[k].get(key, 0) + 1
+        elif what == ROW_NONE:
+            none[k] += 1
+        else:
+            unkeyed[k] += 1
+    return tables, none, unkeyed
+
+
+def is_joint(signal):
+    """Whether a signal is a joint one, (decrements, zeros, starts) with a tuple per letter, and not the reference's."""
+    return isinstance(signal[1], tuple)
+
+
+def signal_flags(signal):
+    """(z, drops, single) as the scores read them.  The reference's signal (s, z, start): z, len(s) - its drop-free NO_DROPS
+    has length 1 -, no (letter, cycle) pair twice.  A joint signal (decrements, zeros, starts), by this package's definition:
+    z = all(zeros); drops = len(decrements), the drop-free () counting as one as NO_DROPS does; single = no (letter, cycle)
+    pair stands twice."""
+    s, z, _ = signal
+    if is_joint(signal):
+        return all(z), max(len(s), 1), len(set(s)) == len(s)
+    return bool(z), len(s), len(set(s)) == len(s)
+
+
 # ---- the key table of a scoring call ----
 
-def ordered_signals(signals):
-    """Signals in the order every sum runs in: ascending key, then those without a key by their repr."""
-    keyed = sorted((key_of_signal(s), s) for s in signals if key_of_signal(s) is not None)
-    return [s for _, s in keyed] + sorted((s for s in signals if key_of_signal(s) is None), key=repr)
+def ordered_signals(signals, letters=None):
+    """Signals in the order every sum runs in: ascending key, then those without a key by their repr.  With `letters` (the
+    sorted label letters of a joint sweep) the signals are joint ones and the key is the joint key."""
+    key = key_of_signal if letters is None else (lambda s: joint_key_of_signal(letters, s))
+    keyed = sorted((key(s), s) for s in signals if key(s) is not None)
+    return [s for _, s in keyed] + sorted((s for s in signals if key(s) is None), key=repr)
 
 
 def check_metric(metric):
@@ -116,21 +270,22 @@ def check_metric(metric):
 def key_table(observed_signals, signals, heatmap_only=True, zero_only=True, exclude_signals=None, select_signals=None,
               allow_multidrop=False):
     """What fsq_signal_scores reads about the keys: observed int64 [S], in_observed, admitted, heatmap uint8 [S] for the
-    ordered `signals` (the union of the observed dict's and of every fit dict's), and the std metrics' n."""
+    ordered `signals` (the union of the observed dict's and of every fit dict's), and the std metrics' n.  Joint signals are
+    admitted by signal_flags' rules: z is all(zeros), single means no (letter, cycle) pair stands twice, the heat-map condition
+    is one or two drops with the drop-free () counting as one."""
     S = len(signals)
     observed, in_observed = np.zeros(S, np.int64), np.zeros(S, np.uint8)
     admitted, heatmap = np.zeros(S, np.uint8), np.zeros(S, np.uint8)
     for i, sig in enumerate(signals):
-        s, z, si = sig
+        z, drops, single = signal_flags(sig)
         if sig in observed_signals:
             observed[i], in_observed[i] = _count(observed_signals[sig]), 1
-        single = len(set(s)) == len(s)
-        admitted[i] = ((select_signals is None or sig in select_signals) and (not zero_only or bool(z))
-                       and (not heatmap_only or len(s) in (1, 2)) and (allow_multidrop or single)
+        admitted[i] = ((select_signals is None or sig in select_signals) and (not zero_only or z)
+                       and (not heatmap_only or drops in (1, 2)) and (allow_multidrop or single)
                        and (exclude_signals is None or sig not in exclude_signals))
-        heatmap[i] = bool(z) and len(s) in (1, 2) and single
-    n_observed = sum(_count(n) for (s, z, si), n in observed_signals.items()
-                     if (not zero_only or z) and (allow_multidrop or len(set(s)) == len(s)))
+        heatmap[i] = z and drops in (1, 2) and single
+    n_observed = sum(_count(n) for sig, n in observed_signals.items()
+                     if (not zero_only or signal_flags(sig)[0]) and (allow_multidrop or signal_flags(sig)[2]))
     if n_observed > MAX_COUNT:
         raise NotImplementedError("observed counts beyond 2^31 - 1")
     return {"signals": list(signals), "observed": observed, "in_observed": in_observed, "admitted": admitted, "heatmap": heatmap,

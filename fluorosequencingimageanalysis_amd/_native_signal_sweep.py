@@ -3,10 +3,13 @@ libfsq_hip.so handle as _native.  A sibling of _native_peptide_sim."""
 import ctypes
 
 from . import _native as N
+from ._native_peptide_labels import FsqPeptideLabelsParams
 from ._native_peptide_sim import FsqPeptideSimParams
 
 MAX_DROPS = 10                      # FSQ_SIGNAL_MAX_DROPS
 MAX_FRAMES = 64                     # FSQ_SIGNAL_MAX_FRAMES
+JOINT_DROP_BITS = {1: 6, 2: 7, 3: 8, 4: 8}      # FSQ_SIGNAL_JOINT_DROP_BITS(K)
+JOINT_MAX_DROPS = {1: 10, 2: 8, 3: 6, 4: 6}     # FSQ_SIGNAL_JOINT_MAX_DROPS(K)
 EMPTY = 0x400                       # FSQ_SIGNAL_EMPTY
 NEVER = 0x800                       # FSQ_SIGNAL_NEVER
 MAX_SLOTS = 1 << 24                 # FSQ_SIGNAL_MAX_SLOTS
@@ -35,6 +38,10 @@ _P, _I64, _I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
 _SIGS = {
     "fsq_peptide_simulate_points": (ctypes.c_int, [ctypes.POINTER(FsqPeptideSimParams), _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "fsq_signal_tally": (ctypes.c_int, [_P, _I32, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    # (declared in fsq_signal_sweep.h beside fsq_peptide_simulate_points, defined in fsq_peptide_labels.hip)
+    "fsq_peptide_simulate_labels_points": (ctypes.c_int, [ctypes.POINTER(FsqPeptideLabelsParams), _P, _I64, _I64, _I64, _I64, _I64, _P, _P,
+                                                          _P, _P]),
+    "fsq_signal_tally_joint": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "fsq_signal_lookup": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "fsq_signal_scores": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.POINTER(FsqScoreParams), _P, _P, _P, _P, _P]),
     "fsq_signal_pair_best": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, ctypes.POINTER(FsqScoreParams), _P, _I32, _I32, _P, _P,

@@ -15,6 +15,7 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_peptide_labels.h"
+#include "../../../include/fsq_signal_sweep.h"
 #include "../libm/fsq_glibc_log.h"
 #include "fsq_philox.h"
 #include "fsq_peptide_lane.h"
@@ -136,6 +137,93 @@ kpl_simulate(const FsqPeptideLabelsParams prm, const long long n, uint8_t* __res
     }
 }
 
+// ---- the sweep's batched form (fsq_peptide_simulate_labels_points of include/fsq_signal_sweep.h) ----
+// kpl_simulate's lane over the flattened [points][molecules] space, as kss_simulate_points (fsq_signal_sweep.hip) is
+// kps_simulate's: each lane with its own point's chemistry parameters, only counts, intensities and categories written.  No
+// loss rows are staged: the dynamic LDS is 64 * (8 * dbl_stride(F) + K * cnt_stride(F)) bytes, 50 688 at K = 4, F = 64, and
+// the channel values (s_ddif, s_phot) are 640 static bytes more.
+constexpr size_t POINTS_STATIC_LDS = MAX_K * DDIF_ROW * 8 + MAX_K * 32;
+constexpr size_t LAUNCH_LDS_LIMIT = 64 * 1024;
+
+size_t points_lds_bytes(int K, int frames) { return (size_t)WAVE * dbl_stride(frames) * 8 + (size_t)K * WAVE * cnt_stride(frames); }
+
+__global__ void __launch_bounds__(WAVE)
+kpl_simulate_points(const FsqPeptideLabelsParams prm, const FsqSweepPoint* __restrict__ g_points, const long long n_per_point,
+                    const long long molecule_stride, const long long first_row, const long long n, uint8_t* __restrict__ g_counts,
+                    double* __restrict__ g_intensity, unsigned long long* __restrict__ g_category)
+{
+    extern __shared__ double s_dbl[];
+    __shared__ double s_ddif[MAX_K * DDIF_ROW];
+    __shared__ LanePhot s_phot[MAX_K];
+    static_assert(sizeof(s_ddif) + sizeof(s_phot) == POINTS_STATIC_LDS, "POINTS_STATIC_LDS");
+    const int lane = threadIdx.x;
+    const int K = prm.n_channels;
+    const int C = prm.num_mocks + prm.num_edmans, F = C + 1;
+    unsigned long long mask[MAX_K], labels = 0ull;
+#pragma unroll
+    for (int k = 0; k < MAX_K; ++k) {
+        mask[k] = k < K ? prm.channel_mask[k] : 0ull;
+        labels |= mask[k];
+    }
+    const int L = __builtin_popcountll(labels);
+    const int DS = dbl_stride(F), CS = cnt_stride(F);
+    uint8_t* const s_cnt = (uint8_t*)(s_dbl + WAVE * DS);                       // [K][WAVE][CS]
+    {
+        const int k = lane / DDIF_ROW, i = lane % DDIF_ROW;                     // 64 lanes: 4 rows of 16
+        s_ddif[lane] = k < K && i < prm.n_ddif[k] && i < FSQ_PEPTIDE_MAX_LABELLED ? prm.ddif[k][i] : 0.0;
+        if (lane < MAX_K) {
+            const bool on = lane < K;
+            const LanePhot ph = {on ? prm.log_beta[lane] : 0.0, on ? prm.beta_sigma[lane] : 0.0, on ? prm.superdye_rate[lane] : 0.0,
+                                 on ? prm.superdye_factor[lane] : 0.0};
+            s_phot[lane] = ph;
+        }
+    }
+    uint8_t* const my_cnt = s_cnt + lane * CS;                                  // channel k's row: + k * WAVE * CS
+    double* const my_dbl = s_dbl + lane * DS;
+    __syncthreads();
+
+    for (long long base = (long long)blockIdx.x * WAVE; base < n; base += (long long)gridDim.x * WAVE) {
+        const int rows = (int)(n - base < WAVE ? n - base : WAVE);
+        const bool active = lane < rows;
+        unsigned long long molecule = 0ull;
+        if (active) {
+            const long long g = first_row + base + lane;
+            const long long pk = g / n_per_point;                                   // the row's point: a per-lane value
+            const FsqSweepPoint pt = g_points[pk];
+            const LaneChem chem = {pt.p, pt.per_cycle_b, pt.u, pt.s, pt.s2};
+            molecule = (unsigned long long)prm.first_molecule + (unsigned long long)(pk * molecule_stride) +
+                       (unsigned long long)(g - pk * n_per_point);
+            lane_chemistry_put<false>(
+                chem, prm.seed, molecule, labels, L, prm.length, prm.num_mocks, C, prm.sc,
+                [&](int c, unsigned long long live) {
+#pragma unroll
+                    for (int k = 0; k < MAX_K; ++k)
+                        if (k < K) my_cnt[k * WAVE * CS + c] = (uint8_t)__builtin_popcountll(live & mask[k]);
+                },
+                nullptr, nullptr, nullptr);
+        }
+        __syncthreads();
+        for (int k = 0; k < K; ++k) {
+            uint8_t* const g = g_counts + ((long long)k * n + base) * F;
+            const uint8_t* const s = s_cnt + k * WAVE * CS;
+            for (int t = lane; t < rows * F; t += WAVE) g[t] = s[(t / F) * CS + t % F];
+        }
+        for (int k = 0; k < K; ++k) {
+            double* const g_int = g_intensity + ((long long)k * n + base) * F;
+            if (active) {
+                int n1, n2;
+                const LanePhot ph = s_phot[k];
+                g_category[(long long)k * n + base + lane] =
+                    lane_photometry_streams(ph, prm.seed, superdye_stream(k), normal_stream(k), s_ddif + k * DDIF_ROW, molecule, F,
+                                            my_cnt + k * WAVE * CS, my_dbl, &n1, &n2);
+            }
+            __syncthreads();
+            for (int t = lane; t < rows * F; t += WAVE) g_int[t] = s_dbl[(t / F) * DS + t % F];
+            __syncthreads();
+        }
+    }
+}
+
 // the checks fsq_peptide_simulate_labels makes before a launch
 bool labels_params_ok(const FsqPeptideLabelsParams* p, int64_t n)
 {
@@ -184,6 +272,31 @@ extern "C" int fsq_peptide_simulate_labels(const FsqPeptideLabelsParams* prm, in
     hipLaunchKernelGGL(kpl_simulate, dim3((unsigned)blocks), dim3(WAVE), lds_bytes(K, frames, L), (hipStream_t)stream, *prm,
                        (long long)n_molecules, d_counts, d_loss_cycle, d_loss_cause, (unsigned long long*)d_edman_fail, d_intensity,
                        d_log_intensity, (unsigned long long*)d_category, d_n_draws);
+    FSQ_HIP_CHECK(hipGetLastError());
+    return FSQ_OK;
+}
+
+extern "C" int fsq_peptide_simulate_labels_points(const FsqPeptideLabelsParams* base, const FsqSweepPoint* d_points, int64_t n_points,
+                                                  int64_t n_per_point, int64_t molecule_stride, int64_t first_row, int64_t n_rows,
+                                                  uint8_t* d_counts, double* d_intensity, uint64_t* d_category, void* stream)
+{
+    if (!labels_params_ok(base, 0)) return FSQ_EINVAL;
+    if (n_points < 1 || n_per_point < 1 || molecule_stride < 0 || first_row < 0 || n_rows < 0) return FSQ_EINVAL;
+    const __int128 total = (__int128)n_points * n_per_point;
+    if ((__int128)first_row + n_rows > total) return FSQ_EINVAL;
+    if ((__int128)base->first_molecule + (__int128)(n_points - 1) * molecule_stride + n_per_point - 1 > (__int128)INT64_MAX) return FSQ_EINVAL;
+    if (!d_points) return FSQ_EINVAL;
+    const int K = base->n_channels, frames = base->num_mocks + base->num_edmans + 1;
+    const size_t lds = points_lds_bytes(K, frames);
+    if (lds + POINTS_STATIC_LDS > LAUNCH_LDS_LIMIT) return FSQ_EINVAL;
+    if ((__int128)n_rows * frames * K * 8 > (__int128)INT64_MAX) return FSQ_EINVAL;
+    if (n_rows == 0) return FSQ_OK;
+    if (!d_counts || !d_intensity || !d_category) return FSQ_EINVAL;
+    const int64_t chunks = (n_rows + WAVE - 1) / WAVE;
+    const int64_t blocks = chunks < MAX_BLOCKS ? chunks : MAX_BLOCKS;
+    hipLaunchKernelGGL(kpl_simulate_points, dim3((unsigned)blocks), dim3(WAVE), lds, (hipStream_t)stream, *base, d_points,
+                       (long long)n_per_point, (long long)molecule_stride, (long long)first_row, (long long)n_rows, d_counts,
+                       d_intensity, (unsigned long long*)d_category);
     FSQ_HIP_CHECK(hipGetLastError());
     return FSQ_OK;
 }

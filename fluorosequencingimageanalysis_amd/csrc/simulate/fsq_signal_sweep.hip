@@ -6,6 +6,8 @@
 //   kss_tally            one lane per row: the row's 64-bit signal key, added to a per-block LDS table (one sub-table for
 //                        each of the first TALLY_POINTS points of the block), which is then flushed to the points' global
 //                        open-addressing tables with one atomic add per distinct (point, key) of the block.
+//   kss_tally_joint      kss_tally for molecules of K colour channels, rows [K][n_rows][frames]: only the row-to-key step
+//                        differs (joint_row_key, the joint key of include/fsq_signal_sweep.h); the tables are the same.
 //   kss_lookup           one lane per (wanted key, point): the dense count matrix.
 //   kss_scores           one lane per point: signal_correlation (jupyter_development.py:279-578), sums left to right.
 // Every probe loop has a fixed bound and no lane reads what another lane stores without an atomic: a full or wrong table costs
@@ -119,11 +121,49 @@ __device__ __forceinline__ void table_add(unsigned long long* __restrict__ g_key
     g_overflow[point] = 1;
 }
 
-__global__ void __launch_bounds__(TALLY_BLOCK)
-kss_tally(const uint8_t* __restrict__ g_rows, const int frames, const int32_t* __restrict__ g_point, const uint8_t* __restrict__ g_valid,
-          const long long n_rows, const int n_points, const int slots, unsigned long long* __restrict__ g_keys,
-          long long* __restrict__ g_counts, long long* __restrict__ g_none, long long* __restrict__ g_unkeyed,
-          int32_t* __restrict__ g_overflow)
+// The joint key of include/fsq_signal_sweep.h of a molecule's K count rows, channel k's at row0 + k * channel_stride: the
+// frames once, the channels inside, a field per lost dye.  K = 1: row_key's key and answer.
+__device__ __forceinline__ int joint_row_key(const uint8_t* __restrict__ row0, const long long channel_stride, const int K,
+                                             const int frames, unsigned long long* key)
+{
+    const int B = FSQ_SIGNAL_JOINT_DROP_BITS(K), D = FSQ_SIGNAL_JOINT_MAX_DROPS(K);
+    int prev[FSQ_PEPTIDE_MAX_CHANNELS], drops = 0;
+    unsigned long long k = 0ull;
+    bool up = false, unkeyed = false;
+#pragma unroll
+    for (int ch = 0; ch < FSQ_PEPTIDE_MAX_CHANNELS; ++ch) {
+        prev[ch] = 0;
+        if (ch < K) {
+            prev[ch] = row0[ch * channel_stride];
+            unkeyed |= prev[ch] > 15;
+            k |= (unsigned long long)(prev[ch] & 15) << (ch == 0 ? 0 : 64 - 4 * (K - ch));
+        }
+    }
+    for (int f = 1; f < frames; ++f) {
+#pragma unroll
+        for (int ch = 0; ch < FSQ_PEPTIDE_MAX_CHANNELS; ++ch) {
+            if (ch < K) {
+                const int c = row0[ch * channel_stride + f];
+                if (c > prev[ch]) up = true;
+                for (int j = c; j < prev[ch]; ++j) {
+                    if (drops < D) k |= (unsigned long long)(f | (ch << 6)) << (4 + B * drops);
+                    ++drops;
+                }
+                prev[ch] = c;
+            }
+        }
+    }
+    *key = k;
+    return up ? ROW_NONE : (unkeyed || drops > D) ? ROW_UNKEYED : ROW_SIGNAL;
+}
+
+// The tally of kss_tally and kss_tally_joint: row_key_of(g, &key) classifies row g and gives its key.
+template <class RowKey>
+__device__ __forceinline__ void tally_rows(const RowKey row_key_of, const int32_t* __restrict__ g_point,
+                                           const uint8_t* __restrict__ g_valid, const long long n_rows, const int n_points,
+                                           const int slots, unsigned long long* __restrict__ g_keys, long long* __restrict__ g_counts,
+                                           long long* __restrict__ g_none, long long* __restrict__ g_unkeyed,
+                                           int32_t* __restrict__ g_overflow)
 {
     __shared__ unsigned long long l_key[TALLY_LDS_SLOTS];
     __shared__ int l_cnt[TALLY_LDS_SLOTS];
@@ -140,7 +180,7 @@ kss_tally(const uint8_t* __restrict__ g_rows, const int frames, const int32_t* _
         if (g < n_rows && (!g_valid || g_valid[g])) {
             point = g_point[g];
             if (point >= 0 && point < n_points) {
-                const int what = row_key(g_rows + g * frames, frames, &key);
+                const int what = row_key_of(g, &key);
                 if (what == ROW_SIGNAL) {
                     has = true;
                     atomicMin(&l_first, point);
@@ -174,6 +214,28 @@ kss_tally(const uint8_t* __restrict__ g_rows, const int frames, const int32_t* _
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(TALLY_BLOCK)
+kss_tally(const uint8_t* __restrict__ g_rows, const int frames, const int32_t* __restrict__ g_point, const uint8_t* __restrict__ g_valid,
+          const long long n_rows, const int n_points, const int slots, unsigned long long* __restrict__ g_keys,
+          long long* __restrict__ g_counts, long long* __restrict__ g_none, long long* __restrict__ g_unkeyed,
+          int32_t* __restrict__ g_overflow)
+{
+    tally_rows([&](long long g, unsigned long long* key) { return row_key(g_rows + g * frames, frames, key); }, g_point, g_valid, n_rows,
+               n_points, slots, g_keys, g_counts, g_none, g_unkeyed, g_overflow);
+}
+
+// g_rows is [K][n_rows][frames]: molecule g's channel k row at (k * n_rows + g) * frames
+__global__ void __launch_bounds__(TALLY_BLOCK)
+kss_tally_joint(const uint8_t* __restrict__ g_rows, const int K, const int frames, const int32_t* __restrict__ g_point,
+                const uint8_t* __restrict__ g_valid, const long long n_rows, const int n_points, const int slots,
+                unsigned long long* __restrict__ g_keys, long long* __restrict__ g_counts, long long* __restrict__ g_none,
+                long long* __restrict__ g_unkeyed, int32_t* __restrict__ g_overflow)
+{
+    const long long channel_stride = n_rows * frames;
+    tally_rows([&](long long g, unsigned long long* key) { return joint_row_key(g_rows + g * frames, channel_stride, K, frames, key); },
+               g_point, g_valid, n_rows, n_points, slots, g_keys, g_counts, g_none, g_unkeyed, g_overflow);
 }
 
 __global__ void __launch_bounds__(256)
@@ -313,6 +375,25 @@ extern "C" int fsq_signal_tally(const uint8_t* d_rows, int32_t frames, const int
     hipLaunchKernelGGL(kss_tally, dim3((unsigned)blocks), dim3(TALLY_BLOCK), 0, (hipStream_t)stream, d_rows, (int)frames, d_point, d_valid,
                        (long long)n_rows, (int)n_points, (int)slots, (unsigned long long*)d_keys, (long long*)d_counts,
                        (long long*)d_none, (long long*)d_unkeyed, d_overflow);
+    FSQ_HIP_CHECK(hipGetLastError());
+    return FSQ_OK;
+}
+
+extern "C" int fsq_signal_tally_joint(const uint8_t* d_rows, int32_t n_channels, int32_t frames, const int32_t* d_point,
+                                      const uint8_t* d_valid, int64_t n_rows, int32_t n_points, int32_t slots, uint64_t* d_keys,
+                                      int64_t* d_counts, int64_t* d_none, int64_t* d_unkeyed, int32_t* d_overflow, void* stream)
+{
+    if (n_channels < 1 || n_channels > FSQ_PEPTIDE_MAX_CHANNELS) return FSQ_EINVAL;
+    if (frames < 1 || frames > FSQ_SIGNAL_MAX_FRAMES || n_rows < 0 || !tables_ok(n_points, slots)) return FSQ_EINVAL;
+    if ((__int128)n_rows * frames * n_channels > (__int128)INT64_MAX) return FSQ_EINVAL;
+    if (!d_keys || !d_counts || !d_none || !d_unkeyed || !d_overflow) return FSQ_EINVAL;
+    if (n_rows == 0) return FSQ_OK;
+    if (!d_rows || !d_point) return FSQ_EINVAL;
+    const int64_t chunks = (n_rows + TALLY_BLOCK - 1) / TALLY_BLOCK;
+    const int64_t blocks = chunks < MAX_BLOCKS ? chunks : MAX_BLOCKS;
+    hipLaunchKernelGGL(kss_tally_joint, dim3((unsigned)blocks), dim3(TALLY_BLOCK), 0, (hipStream_t)stream, d_rows, (int)n_channels,
+                       (int)frames, d_point, d_valid, (long long)n_rows, (int)n_points, (int)slots, (unsigned long long*)d_keys,
+                       (long long*)d_counts, (long long*)d_none, (long long*)d_unkeyed, d_overflow);
     FSQ_HIP_CHECK(hipGetLastError());
     return FSQ_OK;
 }

@@ -45,6 +45,7 @@ CAUSE_NONE, CAUSE_DUD, CAUSE_DESTRUCTION, CAUSE_EDMAN, CAUSE_STRIP = (NP.CAUSE_N
 CAUSE_NAMES = {CAUSE_DUD: 'dye dud', CAUSE_DESTRUCTION: 'dye destruction', CAUSE_EDMAN: 'edman', CAUSE_STRIP: 'surface strip'}
 TABLES = ("counts", "loss_cycle", "loss_cause", "edman_fail", "intensity", "log_intensity", "category", "n_draws")
 PER_LETTER = ("beta", "beta_sigma", "ddif", "superdye_rate", "superdye_factor")      # one value for all letters, or {letter: value}
+JOINT_TALLY_SLOTS = 1 << 24     # the largest table of joint_signals_from_device's tally (FSQ_SIGNAL_MAX_SLOTS)
 
 
 def fresh_seed():
@@ -65,7 +66,7 @@ def _label_of(labels):
     letters = sorted(set(labels))
     if len(letters) > 1:
         raise NotImplementedError("This part currently only works for one label (several letters: multilabel_records; "
-                                  "parameter sweeps over several letters are not built).")
+                                  "parameter sweeps over several letters: signal_sweep.joint_sweep_records).")
     if not letters:
         raise ValueError("a label letter is needed")
     return letters[0]
@@ -529,17 +530,33 @@ def simulate_and_fit_records(sequence, labels, num_mocks, num_edmans, num_simula
 
 
 def joint_signals_from_device(sim):
-    """joint_signals_of_records of a multilabel simulation on the device: torch.unique over the K * frames count row of every
-    molecule with any dye at frame 0; only the unique rows reach Python."""
+    """joint_signals_of_records of a multilabel simulation on the device, over the molecules with any dye at frame 0: the joint
+    key tally of signal_sweep (fsq_signal_tally_joint, one point), whose occupied slots alone reach Python.  The molecules
+    without a 64-bit key (more drops in all than the key holds - a simulated row never steps up, so its drops are its first
+    count minus its last -, a start above 15) go the other way: torch.unique over their K * frames count rows, and only the
+    unique rows reach Python.  So do all of them where the table overflows.  The result is the same."""
     torch = _engine._torch()
+    from . import _host_signal_sweep as H
+    from . import signal_sweep as SW
     counts = sim["counts"]
     K, n, F = (int(x) for x in counts.shape)
     keep = (counts[:, :, 0] != 0).any(dim=0)
-    rows, m = torch.unique(counts.permute(1, 0, 2)[keep].reshape(-1, K * F), dim=0, return_counts=True)
-    out = {}
-    for row, count in zip(rows.cpu().tolist(), m.cpu().tolist()):
-        key = joint_signal(sim["labels"], [row[k * F:(k + 1) * F] for k in range(K)])
-        out[key] = out.get(key, 0) + count
+    out, rest = {}, keep
+    if F <= H.MAX_FRAMES and counts.is_contiguous():
+        drops = (counts[:, :, 0].to(torch.int32) - counts[:, :, F - 1].to(torch.int32)).sum(dim=0)
+        keyed = keep & (drops <= H.JOINT_MAX_DROPS[K]) & (counts[:, :, 0] <= 15).all(dim=0)
+        slots = 64                                                  # twice the keyed molecules: the table cannot fill up below the cap
+        while slots < min(2 * int(keyed.sum()), JOINT_TALLY_SLOTS):
+            slots *= 2
+        tables = SW.new_tables(1, slots, counts.device)
+        SW.tally_joint_device(tables, counts, torch.zeros(n, dtype=torch.int32, device=counts.device), keyed.to(torch.uint8))
+        if not bool(tables["unkeyed"].any() | tables["overflow"].any() | tables["none"].any()):
+            out, rest = SW._decode_tables(tables, tuple(sim["labels"]))[0], keep & ~keyed
+    if bool(rest.any()):
+        rows, m = torch.unique(counts.permute(1, 0, 2)[rest].reshape(-1, K * F), dim=0, return_counts=True)
+        for row, count in zip(rows.cpu().tolist(), m.cpu().tolist()):
+            key = joint_signal(sim["labels"], [row[k * F:(k + 1) * F] for k in range(K)])
+            out[key] = out.get(key, 0) + count
     return out
 
 

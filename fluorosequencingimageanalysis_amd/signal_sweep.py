@@ -28,7 +28,16 @@ reference's: its dict order); points without a result (None) are never chosen.
 The rest of match_diagnostic stands at the end of this file: its incompatibility loop over all pairs of heat-map signals
 (:833-889) as fsq_signal_pair_best and fsq_signal_pair_extremes on the same count matrix (incompatibility_device,
 incompatibility_records), the heat-map tables without plotly (single_drops_table, double_drops_table) and match_diagnostic
-itself, which returns what the notebook cell plots."""
+itself, which returns what the notebook cell plots.
+
+Several label letters (two-colour labelling): joint_sweep_device and joint_sweep_records run the same sweep over
+peptide_simulator.joint_signal's (decrements, zeros, starts), a definition of this package - the reference stops at one
+letter - under the joint 64-bit key of include/fsq_signal_sweep.h: fsq_peptide_simulate_labels_points, one lognormal fit per
+colour channel, fsq_signal_tally_joint.  The sweep's dict carries `labels`, and score_device, score_records,
+incompatibility_device, incompatibility_records and match_diagnostic then read joint signals, through the same lookup, score
+and pair kernels.  joint_signals_of_fits gives the observed dict.  Limits: at most 4 letters; 10, 8, 6, 6 drops over all
+channels for 1, 2, 3, 4 letters; a channel starts at 15 dyes or fewer.  sweep_device and sweep_records keep refusing several
+letters."""
 import ctypes
 import decimal
 import itertools
@@ -149,14 +158,14 @@ def lookup_device(tables, d_wanted):
     return out
 
 
-def _check_tables(tables, what, slots):
+def _check_tables(tables, what, slots, max_drops=NS.MAX_DROPS):
     if bool(tables["overflow"].any()):
         k = int(tables["overflow"].nonzero()[0])
         raise ValueError("point %d has more distinct %s than table_slots=%d: pass a larger power of two" % (k, what, slots))
     if bool(tables["unkeyed"].any()):
         k = int(tables["unkeyed"].nonzero()[0])
         raise NotImplementedError("point %d has %s with more than %d drops, or that start above 15 dyes: they have no 64-bit key"
-                                  % (k, what, NS.MAX_DROPS))
+                                  % (k, what, max_drops))
 
 
 def sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=0, first_molecule=0, molecule_stride=0,
@@ -213,13 +222,24 @@ def sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulation
             "none_count": total - found_n if fit else None, "num_simulations": n, "table_slots": slots}
 
 
-def _decode_tables(tables):
-    """[{signal: count}] per point: only the occupied slots reach Python."""
+def _codec(sweep):
+    """(key_of_signal, signal_of_key, letters) of a sweep: the joint key's under the sweep's `labels`, else the one-letter key's
+    (letters None)."""
+    letters = sweep.get("labels")
+    if letters is None:
+        return H.key_of_signal, H.signal_of_key, None
+    letters = tuple(letters)
+    return (lambda s: H.joint_key_of_signal(letters, s)), (lambda k: H.joint_signal_of_key(letters, k)), letters
+
+
+def _decode_tables(tables, letters=None):
+    """[{signal: count}] per point: only the occupied slots reach Python.  With `letters` the keys are joint keys."""
     keys, counts = tables["keys"].cpu().numpy().view(np.uint64), tables["counts"].cpu().numpy()
     out = []
     for k in range(keys.shape[0]):
         at = np.flatnonzero(keys[k] != NS.EMPTY)
-        out.append({H.signal_of_key(key): int(n) for key, n in zip(keys[k][at].tolist(), counts[k][at].tolist())})
+        signals = [H.signal_of_key(key) for key in keys[k][at].tolist()] if letters is None else H.joint_signals_of_keys(letters, keys[k][at])
+        out.append(dict(zip(signals, counts[k][at].tolist())))
     return out
 
 
@@ -278,12 +298,260 @@ def sweep_records(sequence, labels, num_mocks, num_edmans, points, num_simulatio
 def records_of_sweep(sweep):
     """sweep_records' dict of sweep_device's."""
     keys = sweep["points"]
-    mol = _decode_tables(sweep["molecular"])
-    sig = _decode_tables(sweep["signals"]) if sweep["signals"] is not None else [None] * len(keys)
+    letters = _codec(sweep)[2]
+    mol = _decode_tables(sweep["molecular"], letters)
+    sig = _decode_tables(sweep["signals"], letters) if sweep["signals"] is not None else [None] * len(keys)
     total = sweep["total_count"].cpu().tolist()
     none = sweep["none_count"].cpu().tolist() if sweep["none_count"] is not None else [None] * len(keys)
-    return {"points": keys, "all_simulations": {key: (sig[k], mol[k]) for k, key in enumerate(keys)},
-            "total_count": dict(zip(keys, total)), "none_count": dict(zip(keys, none))}
+    out = {"points": keys, "all_simulations": {key: (sig[k], mol[k]) for k, key in enumerate(keys)},
+           "total_count": dict(zip(keys, total)), "none_count": dict(zip(keys, none))}
+    if letters is not None:
+        out["labels"] = letters
+    return out
+
+
+# ---- sweeps over several label letters: joint signals (include/fsq_signal_sweep.h, THE JOINT KEY) ----
+# A joint signal is peptide_simulator.joint_signal's (decrements, zeros, starts), a definition of this package.  Its limits:
+# at most 4 letters, D(K) = 10, 8, 6, 6 drops over all channels, a channel starts at 15 dyes or fewer.
+
+def _joint_point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points, fixed):
+    """_point_params for several letters: (the base FsqPeptideLabelsParams, float64 [P][5], the points as dict keys, the
+    sorted letters), every point through peptide_simulator._labels_params."""
+    points = list(points)
+    if not points:
+        raise ValueError("at least one point is needed")
+    values, base, letters = np.empty((len(points), 5)), None, None
+    for k, point in enumerate(points):
+        ep = dict(fixed)
+        ep.update(_point_dict(point))
+        if 'per_cycle_b' in ep and 'b' in _point_dict(point):
+            del ep['per_cycle_b']
+        prm, meta = PS._labels_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, ep)
+        values[k] = (prm.p, prm.per_cycle_b, prm.u, prm.s, prm.s2)
+        base, letters = base or prm, meta["labels"]
+    keys = [tuple(sorted(p.items())) if isinstance(p, dict) else tuple(p) for p in points]
+    if len(set(keys)) != len(keys):
+        raise ValueError("a point stands twice")
+    return base, values, keys, letters
+
+
+def simulate_labels_points_device(prm, d_points, n_points, n_per_point, molecule_stride=0, first_row=0, n_rows=None):
+    """fsq_peptide_simulate_labels_points: counts uint8 [K, n_rows, frames], intensity float64 [K, n_rows, frames] and category
+    int64 [K, n_rows] of rows first_row .. first_row + n_rows - 1 of the flattened [n_points][n_per_point] space, channel-major;
+    prm is a FsqPeptideLabelsParams, d_points a float64 CUDA tensor [n_points, 5] of (p, per_cycle_b, u, s, s2).  Enqueued on
+    the current stream, not synchronised."""
+    torch = _engine._torch()
+    if d_points.dtype != torch.float64 or tuple(d_points.shape) != (int(n_points), 5) or not d_points.is_contiguous():
+        raise ValueError("a contiguous float64 tensor [n_points, 5] is needed")
+    n = int(n_points) * int(n_per_point) - int(first_row) if n_rows is None else int(n_rows)
+    dev, K, F = d_points.device, prm.n_channels, prm.num_mocks + prm.num_edmans + 1
+    out = {"counts": torch.empty((K, max(n, 0), F), dtype=torch.uint8, device=dev),
+           "intensity": torch.empty((K, max(n, 0), F), dtype=torch.float64, device=dev),
+           "category": torch.empty((K, max(n, 0)), dtype=torch.int64, device=dev)}
+    _engine.launch(NS.lib().fsq_peptide_simulate_labels_points, "fsq_peptide_simulate_labels_points", dev, ctypes.byref(prm),
+                   d_points.data_ptr(), int(n_points), int(n_per_point), int(molecule_stride), int(first_row), n,
+                   *[out[k].data_ptr() if out[k].numel() else None for k in ("counts", "intensity", "category")])
+    return out
+
+
+def tally_joint_device(tables, d_rows, d_point, d_valid=None):
+    """fsq_signal_tally_joint: adds the joint signals of uint8 [K, n, frames] rows (channel-major, K = 1 .. 4) to the tables of
+    their points (int32 [n]); d_valid uint8 [n] or None.  The tables are new_tables'.  Enqueued, not synchronised."""
+    torch = _engine._torch()
+    if d_rows.dim() != 3:
+        raise ValueError("uint8 rows [K, n, frames] are needed")
+    K, n, frames = (int(x) for x in d_rows.shape)
+    if d_rows.dtype != torch.uint8 or d_point.dtype != torch.int32 or tuple(d_point.shape) != (n,):
+        raise ValueError("uint8 rows [K, n, frames] and int32 points [n] are needed")
+    if d_valid is not None and (d_valid.dtype != torch.uint8 or tuple(d_valid.shape) != (n,)):
+        raise ValueError("a uint8 mask [n] is needed")
+    if not 1 <= frames <= NS.MAX_FRAMES or not 1 <= K <= H.MAX_CHANNELS:
+        raise ValueError("rows have 1 .. %d frames and 1 .. %d channels" % (NS.MAX_FRAMES, H.MAX_CHANNELS))
+    if not (d_rows.is_contiguous() and d_point.is_contiguous() and (d_valid is None or d_valid.is_contiguous())):
+        raise ValueError("contiguous tensors are needed")
+    n_points, slots = (int(x) for x in tables["keys"].shape)
+    _engine.launch(NS.lib().fsq_signal_tally_joint, "fsq_signal_tally_joint", d_rows.device, d_rows.data_ptr() if n else None, K, frames,
+                   d_point.data_ptr() if n else None, None if d_valid is None or not n else d_valid.data_ptr(), n, n_points, slots,
+                   tables["keys"].data_ptr(), tables["counts"].data_ptr(), tables["none"].data_ptr(), tables["unkeyed"].data_ptr(),
+                   tables["overflow"].data_ptr())
+
+
+def _joint_fit_means(letters, fixed, quench_factors, max_possible):
+    """Per letter (log_fluor_means, beta_sigma): beta, beta_sigma and quench_factors are one value for all letters or a dict
+    {letter: value}, as peptide_simulator.multilabel_and_fit_records takes them."""
+    betas, sigmas = PS._per_letter(fixed, 'beta', letters, None), PS._per_letter(fixed, 'beta_sigma', letters, None)
+    quench = PS._per_letter({'quench_factors': quench_factors}, 'quench_factors', letters, None)
+    return [(_tracks.log_fluor_means(betas[k], quench[k], max_possible), sigmas[k]) for k in range(len(letters))]
+
+
+def joint_sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=0, first_molecule=0, molecule_stride=0,
+                       fit=True, max_possible=5, allow_multidrop=True, max_deviation=3, quench_factors=None, solver=None,
+                       table_slots=1024, chunk_rows=1 << 22, device=None, **fixed_parameters):
+    """sweep_device for up to 4 label letters, one colour channel each: the tables hold joint signals under the joint key.
+    beta, beta_sigma, ddif, superdye_rate, superdye_factor and quench_factors are one value for all letters or a dict {letter:
+    value}.  Per chunk of at most chunk_rows rows (the result does not depend on it): simulate (fsq_peptide_simulate_labels_points);
+    tally the molecules with any lit channel into `molecular`; per channel fit the molecules whose channel is lit with
+    lognormal.lognormal_device under that letter's parameters, best_seq into a zeroed [K, rows, frames] buffer so that a dark
+    channel stays a row of zeros; tally into `signals` every molecule with a lit channel whose lit channels were all found.
+    total_count: the molecules with a lit channel; none_count: total_count minus the tallied ones.  Returns sweep_device's dict
+    plus `labels`, the sorted letters."""
+    torch = _engine._torch()
+    from . import lognormal as LN
+    n, stride, slots, chunk = _check_sweep_shape(num_simulations, molecule_stride, table_slots, chunk_rows)
+    base, values, keys, letters = _joint_point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points,
+                                                      fixed_parameters)
+    P, K, F = len(keys), len(letters), base.num_mocks + base.num_edmans + 1
+    dev = torch.device(device or "cuda")
+    fit_kw = []
+    if fit:
+        fit_kw = [dict(prm=LN.fit_params(means, sigma, max_possible, allow_multidrop, max_deviation, LN.DEFAULT_BUDGET),
+                       **LN._solver_kw(solver or 'enumerate'))
+                  for means, sigma in _joint_fit_means(letters, fixed_parameters, quench_factors, max_possible)]
+        if not allow_multidrop and F == 1:
+            raise ValueError("max() arg is an empty sequence")        # (as lognormal.photometries_lognormal_fit, :5442)
+    d_points = torch.from_numpy(values).to(dev)
+    molecular, signals = new_tables(P, slots, dev), new_tables(P, slots, dev) if fit else None
+    total, found_n = torch.zeros(P, dtype=torch.int64, device=dev), torch.zeros(P, dtype=torch.int64, device=dev)
+    bad = torch.zeros((), dtype=torch.bool, device=dev)
+    for first in range(0, P * n, chunk):
+        rows = min(chunk, P * n - first)
+        sim = simulate_labels_points_device(base, d_points, P, n, stride, first, rows)
+        d_point = torch.div(torch.arange(first, first + rows, device=dev), n, rounding_mode="floor").to(torch.int32)
+        lit = (sim["category"] != 0).any(dim=0)
+        tally_joint_device(molecular, sim["counts"], d_point, lit.to(torch.uint8))
+        total += torch.bincount(d_point[lit], minlength=P)
+        if not fit:
+            continue
+        best, ok = torch.zeros((K, rows, F), dtype=torch.uint8, device=dev), lit.clone()
+        for k in range(K):
+            at = (sim["category"][k] != 0).nonzero().reshape(-1)
+            kept = int(at.shape[0])
+            if not kept:
+                continue
+            d_len = torch.full((kept,), F, dtype=torch.int32, device=dev)
+            out = LN.lognormal_device(sim["intensity"][k][at].contiguous(), sim["category"][k][at].contiguous(), d_len, None, None,
+                                      **fit_kw[k])
+            found = out["status"] == LN.STATUS_FOUND
+            bad |= (out["status"] > LN.STATUS_NONE).any()
+            best[k][at[found]] = out["best_seq"][found]
+            ok[at[~found]] = False
+        tally_joint_device(signals, best, d_point, ok.to(torch.uint8))
+        found_n += torch.bincount(d_point[ok], minlength=P)
+    if bool(bad):
+        raise NotImplementedError("a simulated track has more surviving sequences than the budget, or an invalid length")
+    _check_tables(molecular, "molecular joint signals", slots, NS.JOINT_MAX_DROPS[K])
+    if fit:
+        _check_tables(signals, "fitted joint signals", slots, NS.JOINT_MAX_DROPS[K])
+    return {"points": keys, "molecular": molecular, "signals": signals, "total_count": total,
+            "none_count": total - found_n if fit else None, "num_simulations": n, "table_slots": slots, "labels": letters}
+
+
+def _host_joint_fits(intensity, category, counts, fits_of, allow_multidrop, max_deviation, max_possible):
+    """(best uint8 [K][m][F], ok bool [m]) of the host lognormal fit of every lit channel of m molecules: a dark channel stays a
+    row of zeros, ok is False where a lit channel was not found.  fits_of[k] is (log_fluor_means, beta_sigma)."""
+    from . import _host_lognormal
+    K, m, F = counts.shape
+    best, ok = np.zeros((K, m, F), np.uint8), np.ones(m, bool)
+    for k in range(K):
+        means, sigma = fits_of[k]
+        for i in np.flatnonzero(category[k] != 0).tolist():
+            f = _host_lognormal.intensities_to_signal(intensity[k][i].tolist(), sigma, max_possible, allow_multidrop, max_deviation,
+                                                      tuple(c != 0 for c in counts[k][i].tolist()), means)
+            if f[2] is None:
+                ok[i] = False
+            else:
+                best[k][i] = f[2]
+    return best, ok
+
+
+def _joint_sweep_host(sequence, labels, num_mocks, num_edmans, points, n, seed, first_molecule, stride, fit, max_possible,
+                      allow_multidrop, max_deviation, quench_factors, fixed):
+    """The joint sweep through the host twins, a point at a time: multilabel_records(host=True), the restated fit, the twin's
+    joint tally."""
+    base, values, keys, letters = _joint_point_params(sequence, labels, num_mocks, num_edmans, seed, first_molecule, points, fixed)
+    K = len(letters)
+    sims, totals, nones = {}, {}, {}
+    fits_of = _joint_fit_means(letters, fixed, quench_factors, max_possible) if fit else None
+    decode = lambda table: {H.joint_signal_of_key(letters, x): c for x, c in table.items()}         # noqa: E731
+    for k, key in enumerate(keys):
+        ep = {x: v for x, v in fixed.items() if x != 'b'}
+        ep.update(zip(("p", "per_cycle_b", "u", "s", "s2"), values[k].tolist()))
+        rec = PS.multilabel_records(sequence, labels, num_mocks, num_edmans, n, seed, first_molecule + k * stride, host=True, **ep)
+        lit = np.flatnonzero((rec["category"] != 0).any(axis=0))
+        counts = rec["counts"][:, lit]
+        zero = np.zeros(len(lit), np.int32)
+        (mol,), _, unkeyed = H.tally_joint_rows(counts, zero, None, 1)
+        signals, none_count = ({}, 0) if fit else (None, None)
+        if fit and len(lit):
+            best, ok = _host_joint_fits(rec["intensity"][:, lit], rec["category"][:, lit], counts, fits_of, allow_multidrop,
+                                        max_deviation, max_possible)
+            (signals,), _, more = H.tally_joint_rows(best, zero, ok, 1)
+            unkeyed[0] += more[0]
+            signals, none_count = decode(signals), int(len(lit) - ok.sum())
+        if unkeyed[0]:
+            raise NotImplementedError("point %d has joint signals with more than %d drops, or that start above 15 dyes"
+                                      % (k, H.JOINT_MAX_DROPS[K]))
+        sims[key] = (signals, decode(mol))
+        totals[key], nones[key] = len(lit), none_count
+    return {"points": keys, "all_simulations": sims, "total_count": totals, "none_count": nones, "labels": letters}
+
+
+def joint_sweep_records(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed=0, first_molecule=0, molecule_stride=0,
+                        fit=True, max_possible=5, allow_multidrop=True, max_deviation=3, quench_factors=None, solver=None,
+                        table_slots=1024, chunk_rows=1 << 22, device=None, host=False, **fixed_parameters):
+    """joint_sweep_device's result as sweep_records gives sweep_device's: `all_simulations` {point: (signals,
+    molecular_signals)} keyed by joint signals, `total_count`, `none_count`, `points` and `labels`.  host=True: the same through
+    multilabel_records(host=True), the host lognormal fit and the twin's joint tally, without a GPU."""
+    if host:
+        n, stride, _, _ = _check_sweep_shape(num_simulations, molecule_stride, table_slots, chunk_rows)
+        return _joint_sweep_host(sequence, labels, num_mocks, num_edmans, points, n, seed, first_molecule, stride, fit, max_possible,
+                                 allow_multidrop, max_deviation, quench_factors, fixed_parameters)
+    return records_of_sweep(joint_sweep_device(sequence, labels, num_mocks, num_edmans, points, num_simulations, seed, first_molecule,
+                                               molecule_stride, fit, max_possible, allow_multidrop, max_deviation, quench_factors,
+                                               solver, table_slots, chunk_rows, device, **fixed_parameters))
+
+
+def joint_signals_of_fits(letters, best_seq, found, category, host=False, table_slots=1024, device=None):
+    """The observed side of a joint sweep: {joint_signal: n} of row-aligned per-channel lognormal fits of the same tracks.
+    best_seq uint8 [K][n][F], found and category [K][n] (non-zero: the channel's fit was found; the channel is lit), NumPy
+    arrays or tensors, the channels in sorted-letter order.  A track counts when it has a lit channel and every lit channel was
+    found; a dark channel counts as a row of zeros.  Through fsq_signal_tally_joint, or the twin with host=True.  Aligning a
+    two-channel track table by track is the caller's."""
+    letters = tuple(letters)
+    if host:
+        best, found, category = (np.asarray(x.cpu() if hasattr(x, "cpu") else x) for x in (best_seq, found, category))
+        lit = category != 0
+        ok = lit.any(axis=0) & ~(lit & (found == 0)).any(axis=0)
+        rows = np.where(lit[:, :, None], best, 0).astype(np.uint8)
+        (table,), _, unkeyed = H.tally_joint_rows(rows, np.zeros(rows.shape[1], np.int32), ok, 1)
+        if unkeyed[0]:
+            raise NotImplementedError("tracks with more than %d drops, or that start above 15 dyes: they have no 64-bit key"
+                                      % H.JOINT_MAX_DROPS[len(letters)])
+        return {H.joint_signal_of_key(letters, x): c for x, c in table.items()}
+    torch = _engine._torch()
+    dev = torch.device(device or "cuda")
+    best, found, category = (torch.as_tensor(x).to(dev) for x in (best_seq, found, category))
+    lit = category != 0
+    ok = lit.any(dim=0) & ~(lit & (found == 0)).any(dim=0)
+    rows = torch.where(lit[:, :, None], best, torch.zeros_like(best)).to(torch.uint8).contiguous()
+    tables = new_tables(1, int(table_slots), dev)
+    tally_joint_device(tables, rows, torch.zeros(int(rows.shape[1]), dtype=torch.int32, device=dev), ok.to(torch.uint8))
+    _check_tables(tables, "joint signals", int(table_slots), NS.JOINT_MAX_DROPS[len(letters)])
+    return _decode_tables(tables, letters)[0]
+
+
+def joint_split_heatmap(letters, num_cycles, cycle):
+    """split_heatmap for joint signals: the heat-map signals - one or two single drops that leave every channel at zero -
+    whose last drop is before `cycle`, and the others, as two tuples; each the single drops by (cycle, letter), then the
+    double drops by their last, then their first drop."""
+    letters = tuple(letters)
+    drops = [(c, k) for c in range(1, num_cycles + 1) for k in range(len(letters))]
+
+    def signal(ds):
+        starts = tuple(sum(1 for _, k in ds if k == j) for j in range(len(letters)))
+        return tuple((letters[k], c) for c, k in ds), (True,) * len(letters), starts
+    each = [(ds[-1][0], signal(ds)) for ds in [(d,) for d in drops] + [(a, b) for b in drops for a in drops if a < b]]
+    return tuple(s for last, s in each if last < cycle), tuple(s for last, s in each if last >= cycle)
 
 
 # ---- scoring ----
@@ -314,22 +582,29 @@ def _scores_on_device(table, d_fit, d_fit_total, metric, normalization, small_co
     return out
 
 
+def _counts_on_host(observed_signals, sweep, molecular):
+    """(the ordered signals, the count matrix int64 [S, P], the points' totals int64 [P]) of sweep_records' dict, or of
+    joint_sweep_records' (it carries `labels`, and the order is then the joint key's)."""
+    dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
+    signals = H.ordered_signals(set(observed_signals).union(*dicts), _codec(sweep)[2])
+    return (signals,) + H.fit_matrix(signals, dicts)
+
+
 def _counts_on_device(observed_signals, sweep, molecular, device):
     """(the ordered signals of the observed dict and every point's dict, the count matrix int64 [S, P] and the points' totals
     int64 [P] as CUDA tensors) of sweep_device's dict (its tables are read where they are) or sweep_records'."""
     torch = _engine._torch()
+    key_of_signal, signal_of_key, letters = _codec(sweep)
     if "all_simulations" in sweep:
-        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
-        signals = H.ordered_signals(set(observed_signals).union(*dicts))
-        fit, fit_total = H.fit_matrix(signals, dicts)
+        signals, fit, fit_total = _counts_on_host(observed_signals, sweep, molecular)
         dev = torch.device(device or "cuda")
         return signals, torch.from_numpy(fit).to(dev), torch.from_numpy(fit_total).to(dev)
     tables = sweep["molecular" if molecular else "signals"]
     if tables is None:
         raise ValueError("the sweep was run with fit=False: pass molecular=True")
     occupied = torch.unique(tables["keys"][tables["keys"] != NS.EMPTY]).cpu().tolist()
-    signals = H.ordered_signals(set(observed_signals) | {H.signal_of_key(k) for k in occupied})
-    wanted = [H.key_of_signal(s) for s in signals]
+    signals = H.ordered_signals(set(observed_signals) | {signal_of_key(k) for k in occupied}, letters)
+    wanted = [key_of_signal(s) for s in signals]
     d_wanted = torch.from_numpy(np.array([NS.NEVER if k is None else k for k in wanted], np.uint64).view(np.int64)).to(tables["keys"].device)
     d_fit, d_total = lookup_device(tables, d_wanted), tables["counts"].sum(dim=1)
     if int(d_total.max()) > NS.MAX_COUNT:
@@ -360,9 +635,7 @@ def score_records(observed_signals, sweep, metric='naive', normalize_counts=Fals
         raise ValueError("on_error must be 'raise' or 'none'")
     if host:
         opts, norm = _score_options(kw), H.normalization_of(normalize_counts, heatmap_normalize_counts)
-        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
-        signals = H.ordered_signals(set(observed_signals).union(*dicts))
-        fit, fit_total = H.fit_matrix(signals, dicts)
+        signals, fit, fit_total = _counts_on_host(observed_signals, sweep, molecular)
         score, factor, status, contrib = H.scores(H.key_table(observed_signals, signals, **opts), fit, fit_total, metric, norm,
                                                   small_count_cutoff, contributions)
     else:
@@ -540,9 +813,7 @@ def incompatibility_records(observed_signals, sweep, select_signals=None, num_cy
         if opts.get("select_signals") is not None:
             raise TypeError("select_signals is the candidate list")
         L = _candidates(select_signals, num_cycles)
-        dicts = [sweep["all_simulations"][key][1 if molecular else 0] for key in sweep["points"]]
-        signals = H.ordered_signals(set(observed_signals).union(*dicts))
-        fit, fit_total = H.fit_matrix(signals, dicts)
+        signals, fit, fit_total = _counts_on_host(observed_signals, sweep, molecular)
         out = H.pair_best(H.key_table(observed_signals, signals, **opts), _candidate_rows(signals, L), fit, fit_total, metric, norm,
                           small_count_cutoff, reverse_order)
         out["score"], out["n_distances"] = H.pair_extremes(out["dist"], len(L), reverse_order)
@@ -581,6 +852,11 @@ def _cycles_header(num_mocks, num_edmans, num_mocks_omitted):
             + ["E" + str(i + 1) for i in range(num_edmans)])
 
 
+def _one_letter_only(signals):
+    if any(H.is_joint(s) for s in signals):
+        raise NotImplementedError("the heat-map tables are built for one label letter, not for joint signals")
+
+
 def single_drops_table(signals, num_mocks, num_edmans, num_mocks_omitted, plot_remainders=True, float_data=False):
     """The heatmap_array of single_drops_heatmap_v2 (:585-620) and its header: (int64 or float64 [1, cycles (+ 1)], the column
     names M.., E.., R).  Only signals that start at one dye or none count: a drop at cycle c that ends at zero in column c - 1,
@@ -589,6 +865,7 @@ def single_drops_table(signals, num_mocks, num_edmans, num_mocks_omitted, plot_r
     total_cycles = num_mocks - num_mocks_omitted + num_edmans
     size = total_cycles + 1 if plot_remainders else total_cycles
     array = np.zeros((1, size), np.float64 if float_data else np.int64)
+    _one_letter_only(signals)
     for (signal, is_zero, starting_intensity), count in signals.items():
         if starting_intensity > 1 or len(signal) != 1:
             continue
@@ -614,6 +891,7 @@ def double_drops_table(signals, num_mocks, num_edmans, num_mocks_omitted, plot_m
     total_cycles = num_mocks - num_mocks_omitted + num_edmans
     size_x, size_y = total_cycles, total_cycles + 1 if plot_remainders else total_cycles
     array = np.zeros((size_x, size_y), np.float64 if float_data else np.int64)
+    _one_letter_only(signals)
     for (signal, is_zero, starting_intensity), count in signals.items():
         if starting_intensity > 2:
             continue
@@ -659,7 +937,10 @@ def match_diagnostic(all_simulations, observed_signals, metric, reverse_order, n
     normalized_plot_signals and normalized_plot_molecular_signals, its counts scaled to the observed total (:949-953);
     diff_plot_signals (:956-959); incompatibility_scores ({} when not computed); exclude_signals (:907-916); `tables`, the
     twelve heat-map arrays of :1005-1190 under TABLE_NAMES, and `z_ranges` (:993-1003; None where the reference's max() would
-    have nothing to take).  reference_tuple() gives the reference's return value.
+    have nothing to take).  reference_tuple() gives the reference's return value.  For a joint sweep (joint_sweep_device's or
+    joint_sweep_records' dict, observed_signals keyed by joint signals) the candidates and the split are joint_split_heatmap's,
+    and `tables`, `z_ranges` and `headers` are None: the heat-map tables stay one-letter (single_drops_table and
+    double_drops_table raise NotImplementedError for joint signals).
 
     Where this differs from the reference, on purpose: the incompatibility loop scores `observed_signals`, not a notebook
     global (:846); num_cycles=None means num_mocks - num_mocks_omitted + num_edmans, the heat maps' own count (:590-591), not
@@ -675,14 +956,17 @@ def match_diagnostic(all_simulations, observed_signals, metric, reverse_order, n
     kw = dict(metric=metric, normalize_counts=normalize_counts, heatmap_normalize_counts=heatmap_normalize_counts,
               small_count_cutoff=small_count_cutoff, host=host, on_error=on_error, device=device, heatmap_only=heatmap_only,
               zero_only=zero_only, matching_p=matching_p)
+    letters = _codec(sweep)[2]                                      # a joint sweep: its heat-map signals are joint_split_heatmap's
+    split = split_heatmap if letters is None else (lambda cycles, cycle: joint_split_heatmap(letters, cycles, cycle))
     incompatibility_scores = {}
     if compute_incompatibility_scores:
-        incompatibility_scores = incompatibility_records(observed_signals, records if host else sweep, None, num_cycles,
+        incompatibility_scores = incompatibility_records(observed_signals, records if host else sweep,
+                                                         None if letters is None else split(num_cycles, 0)[1], num_cycles,
                                                          reverse_order=reverse_order, pairs=False, **kw)["scores"]
     exclude = set()
     if incompatibility_threshold is not None:
         exclude = {s for s, mi in incompatibility_scores.items() if mi > incompatibility_threshold}
-    exclude_signals = exclude | set(split_heatmap(num_cycles, split_cycle)[0])
+    exclude_signals = exclude | set(split(num_cycles, split_cycle)[0])
     scores = score_records(observed_signals, records if host else sweep, exclude_signals=exclude_signals if apply_exclusion else None,
                            **kw)
     optimal_pbu, result, factor, contributions = best_point(scores, reverse_order)
@@ -690,6 +974,11 @@ def match_diagnostic(all_simulations, observed_signals, metric, reverse_order, n
     scaled = lambda d: {s: int(py2_round(n * factor)) for s, n in d.items()}       # noqa: E731
     normalized, normalized_molecular = scaled(plot_signals), scaled(plot_molecular)
     diff = {s: float(n - normalized[s]) / n for s, n in observed_signals.items() if s in normalized and n > 0}
+    if letters is not None:                                         # the heat maps have one axis per drop of one letter
+        return {"optimal_pbu": optimal_pbu, "result": result, "normalization_factor": factor, "optimal_contributions": contributions,
+                "normalized_plot_signals": normalized, "normalized_plot_molecular_signals": normalized_molecular,
+                "diff_plot_signals": diff, "incompatibility_scores": incompatibility_scores, "exclude_signals": exclude_signals,
+                "tables": None, "z_ranges": None, "num_cycles": num_cycles, "headers": None, "labels": letters}
     single, double = [], []
     for (s, z, si), count in itertools.chain(observed_signals.items(), normalized.items(), normalized_molecular.items()):
         if not z or len(s) > len(set(s)):

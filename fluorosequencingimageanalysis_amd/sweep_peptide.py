@@ -15,7 +15,12 @@ normalization_factor, contributions); prints the best point and its score.  --in
 signal_sweep.match_diagnostic's dict (the incompatibility scores of the heat-map signals over all their pairs, the signals
 above --incompatibility_threshold united with those before --split_cycle as exclude_signals, the best point's counts scaled to
 the observed total and the twelve heat-map tables), and prints the number of excluded signals and the five highest scores; it
-needs --heatmap_normalize_counts, or --all_signals with --normalize_counts.  --host runs the NumPy twins; no GPU needed."""
+needs --heatmap_normalize_counts, or --all_signals with --normalize_counts.  --host runs the NumPy twins; no GPU needed.
+
+Several label letters (LABEL "KC", up to 4, one colour channel each) run signal_sweep's joint path: SIGNALS.pkl then holds
+{(decrements, zeros, starts): count} of joint signals (signal_sweep.joint_signals_of_fits makes one), --fluor_intensity,
+--beta_sigma, --superdye_rate and --superdye_factor take one number or K=..,C=.., and the pickle gains `labels`, the sorted
+letters; `diagnostic` then has no heat-map tables.  One letter runs and writes what it did before."""
 import argparse
 import itertools
 import os
@@ -48,10 +53,26 @@ def value_range(text):
     return [float(x) for x in np.linspace(lo, hi, n)]
 
 
+def per_letter(text):
+    """'X' -> the float X; 'K=X,C=Y' -> {'K': X, 'C': Y}."""
+    try:
+        if '=' not in text:
+            return float(text)
+        out = {}
+        for part in text.split(','):
+            letter, value = part.split('=')
+            if len(letter.strip()) != 1 or letter.strip() in out:
+                raise ValueError
+            out[letter.strip()] = float(value)
+        return out
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is neither a number nor LETTER=NUMBER,LETTER=NUMBER" % text)
+
+
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('sequence', nargs=1, type=str, help="The peptide as a string of amino acids.")
-    p.add_argument('labels', nargs=1, type=str, help="The labelled amino acid (one letter).")
+    p.add_argument('labels', nargs=1, type=str, help="The labelled amino acid; several letters (up to 4): one colour each.")
     p.add_argument('--observed', required=True, help="Pickle of the observed signals.")
     p.add_argument('--edman_efficiency', type=value_range, default=[0.90], help="LO:HI:N or a number.")
     p.add_argument('--dye_destruction', type=value_range, default=[0.1], help="Rate per cycle: LO:HI:N or a number.")
@@ -63,13 +84,13 @@ def build_parser():
     p.add_argument('--surface_degradation_1', type=float, default=0.30)
     p.add_argument('--surface_degradation_1_num_cycles', type=int, default=3)
     p.add_argument('--surface_degradation_2', type=float, default=0.10)
-    p.add_argument('--fluor_intensity', type=float, default=70000, help="Intensity of one fluor.")
+    p.add_argument('--fluor_intensity', type=per_letter, default=70000, help="Intensity of one fluor: a number, or K=..,C=..")
     p.add_argument('--ddif_2', type=float, default=0.30)
     p.add_argument('--ddif_3', type=float, default=0.30)
-    p.add_argument('--beta_sigma', type=float, default=0.20)
+    p.add_argument('--beta_sigma', type=per_letter, default=0.20, help="A number, or K=..,C=..")
     p.add_argument('--no_multidrop', action='store_true', default=False, help="No drops of more than one dye in the fit.")
-    p.add_argument('--superdye_rate', type=float, default=0.0)
-    p.add_argument('--superdye_factor', type=float, default=1.0)
+    p.add_argument('--superdye_rate', type=per_letter, default=0.0, help="A number, or K=..,C=..")
+    p.add_argument('--superdye_factor', type=per_letter, default=1.0, help="A number, or K=..,C=..")
     p.add_argument('--output_directory', nargs=1, default=[os.getcwd()], help="Created if it does not exist.")
     p.add_argument('--metric', default='my_euclidean', choices=_host_signal_sweep.METRICS)
     norm = p.add_mutually_exclusive_group()
@@ -105,6 +126,9 @@ def load_observed(path):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    joint = len(set(args.labels[0])) > 1
+    if not joint and any(isinstance(getattr(args, k), dict) for k in ("fluor_intensity", "beta_sigma", "superdye_rate", "superdye_factor")):
+        parser.error("LETTER=NUMBER values need several label letters")
     if args.incompatibility:                                     # (before the sweep is run, not after it)
         try:
             signal_sweep.check_diagnostic_options(args.normalize_counts, args.heatmap_normalize_counts, not args.all_signals,
@@ -126,11 +150,11 @@ def main(argv=None):
                  superdye_factor=args.superdye_factor)
     print("Seed: " + str(args.seed))
     print("Parameters loaded. Sweeping " + str(len(grid)) + " points at " + str(datetime.now()))
-    sweep = signal_sweep.sweep_records(args.sequence[0], args.labels[0], args.num_mocks - args.num_mocks_omitted, args.num_edmans, points,
-                                       args.num_sims, seed=args.seed, molecule_stride=args.molecule_stride, max_possible=MAX_POSSIBLE,
-                                       allow_multidrop=not args.no_multidrop, max_deviation=MAX_DEVIATION, quench_factors=ddif,
-                                       table_slots=args.table_slots, chunk_rows=args.chunk_rows, device=args.device, host=args.host,
-                                       **fixed)
+    run = signal_sweep.joint_sweep_records if joint else signal_sweep.sweep_records
+    sweep = run(args.sequence[0], args.labels[0], args.num_mocks - args.num_mocks_omitted, args.num_edmans, points, args.num_sims,
+                seed=args.seed, molecule_stride=args.molecule_stride, max_possible=MAX_POSSIBLE, allow_multidrop=not args.no_multidrop,
+                max_deviation=MAX_DEVIATION, quench_factors=ddif, table_slots=args.table_slots, chunk_rows=args.chunk_rows,
+                device=args.device, host=args.host, **fixed)
     print("Sweep complete. Scoring at " + str(datetime.now()))
     scores = signal_sweep.score_records(observed, sweep, metric=args.metric, normalize_counts=args.normalize_counts,
                                         heatmap_normalize_counts=args.heatmap_normalize_counts,
@@ -143,10 +167,14 @@ def main(argv=None):
            "total_count": {name[k]: v for k, v in sweep["total_count"].items()},
            "none_count": {name[k]: v for k, v in sweep["none_count"].items()},
            "scores": {name[k]: v for k, v in scores.items()}}
+    if joint:
+        out["labels"] = sweep["labels"]
     out["best_point"] = signal_sweep.best_point(out["scores"], args.reverse_order)
     if args.incompatibility:
         print("Scoring the signal pairs at " + str(datetime.now()))
         named = {"points": grid, "all_simulations": out["all_simulations"]}
+        if joint:
+            named["labels"] = sweep["labels"]
         out["diagnostic"] = signal_sweep.match_diagnostic(
             named, observed, args.metric, args.reverse_order, args.normalize_counts, args.heatmap_normalize_counts,
             not args.all_signals, not args.nonzero_signals, args.score_multidrop, args.small_count_cutoff, 0.10, args.split_cycle,

@@ -20,7 +20,7 @@
 #define FSQ_SIGNAL_SWEEP_H
 #include <stdint.h>
 
-#include "fsq_peptide_sim.h"
+#include "fsq_peptide_labels.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -70,6 +70,49 @@ int fsq_peptide_simulate_points(const FsqPeptideSimParams* base, const FsqSweepP
 int fsq_signal_tally(const uint8_t* d_rows, int32_t frames, const int32_t* d_point, const uint8_t* d_valid, int64_t n_rows,
                      int32_t n_points, int32_t slots, uint64_t* d_keys, int64_t* d_counts, int64_t* d_none, int64_t* d_unkeyed,
                      int32_t* d_overflow, void* stream);
+
+/* THE JOINT KEY.  A molecule seen in K colour channels (K = 1 .. FSQ_PEPTIDE_MAX_CHANNELS label letters, in sorted-letter
+ * order) has K count rows and the joint signal (decrements, zeros, starts) of peptide_simulator.joint_signal - a definition
+ * of this package, the reference stops at one letter.  Its key is again exact and 64 bits wide, so that fsq_signal_lookup,
+ * fsq_signal_scores, fsq_signal_pair_best and fsq_signal_pair_extremes serve it as they are.  With B = 6 + ceil(log2 K) bits
+ * per drop (6, 7, 8, 8):
+ *   bits 0 .. 3                     the starting count of channel 0;
+ *   bits 4 + B i .. 3 + B (i + 1)   drop i: the low 6 bits its cycle (1 .. 63), the bits above its channel; 0: no drop i, and
+ *                                   none after it.  Drops ascend by (cycle, channel); a drop of d dyes stands d times;
+ *   bits 64 - 4 (K - k) .. 67 - 4 (K - k)   the starting count of channel k = 1 .. K - 1: the top nibbles.
+ * The drop capacity D(K) = FSQ_SIGNAL_JOINT_MAX_DROPS(K) is 10, 8, 6, 6.  With K = 1 this is the key above, bit for bit.
+ * `zeros` is not stored: a channel ends at zero exactly when its drops number its starting count.  FSQ_SIGNAL_EMPTY and
+ * FSQ_SIGNAL_NEVER are no molecule's key for any K: bit 10 or 11 alone is a drop field whose cycle is 0 (K >= 2: bit 10 is a
+ * channel bit of drop 0; bit 11 is one too for K >= 3) or a drop that follows an absent one (K = 2: bit 11 is cycle 1 of drop
+ * 1 with drop 0 absent).  A molecule with more than D(K) drops in all, or a channel that starts above 15, has no key
+ * (d_unkeyed); one with an upstep in any channel has no signal (d_none).  A 128-bit key would lift the drop cap and need
+ * lookup, score and pair kernels of its own. */
+#define FSQ_SIGNAL_JOINT_DROP_BITS(K) ((K) <= 1 ? 6 : (K) == 2 ? 7 : 8)
+#define FSQ_SIGNAL_JOINT_MAX_DROPS(K) ((K) <= 1 ? 10 : (K) == 2 ? 8 : 6)
+
+/* fsq_signal_tally for molecules of n_channels colour channels: the joint key of each molecule's n_channels rows.
+ *   d_rows      uint8 [n_channels][n_rows][frames], channel-major: what fsq_peptide_simulate_labels and
+ *               fsq_peptide_simulate_labels_points write, and what n_channels lognormal fits fill
+ * and every other argument as fsq_signal_tally takes it, with the same tables and the same guarantees: bounded probe loops,
+ * one 64-bit compare-and-swap per probe, no lane waits for another's store, an overflow sets d_overflow and costs a count.
+ * With n_channels = 1 it leaves the (key, count) sets fsq_signal_tally leaves. */
+int fsq_signal_tally_joint(const uint8_t* d_rows, int32_t n_channels, int32_t frames, const int32_t* d_point, const uint8_t* d_valid,
+                           int64_t n_rows, int32_t n_points, int32_t slots, uint64_t* d_keys, int64_t* d_counts, int64_t* d_none,
+                           int64_t* d_unkeyed, int32_t* d_overflow, void* stream);
+
+/* fsq_peptide_simulate_labels over the flattened [n_points][n_per_point] space, as fsq_peptide_simulate_points is
+ * fsq_peptide_simulate over it: the same row-to-(point, molecule) rule, the same molecule_stride, first_row and n_rows, and
+ * d_points[k] in place of base's p, per_cycle_b, u, s and s2.  Only three tables are written, channel-major over the call's
+ * rows, K = base->n_channels:
+ *   d_counts    uint8  [K][n_rows][frames]
+ *   d_intensity double [K][n_rows][frames]
+ *   d_category  uint64 [K][n_rows]
+ * each what fsq_peptide_simulate_labels writes for that molecule under that point's parameters, bit for bit; with K = 1 what
+ * fsq_peptide_simulate_points writes.  Defined in fsq_peptide_labels.hip.  A shape whose staging would need more LDS than a
+ * launch gets without an attribute (64 KiB) returns FSQ_EINVAL; none within the limits of fsq_peptide_labels.h does. */
+int fsq_peptide_simulate_labels_points(const FsqPeptideLabelsParams* base, const FsqSweepPoint* d_points, int64_t n_points,
+                                       int64_t n_per_point, int64_t molecule_stride, int64_t first_row, int64_t n_rows,
+                                       uint8_t* d_counts, double* d_intensity, uint64_t* d_category, void* stream);
 
 /* d_out[w][k] = the count of key d_wanted[w] in point k's table, 0 where it is absent: int64 [n_wanted][n_points]. */
 int fsq_signal_lookup(const uint64_t* d_keys, const int64_t* d_counts, int32_t n_points, int32_t slots, const uint64_t* d_wanted,
