@@ -1664,6 +1664,39 @@ extern "C" int fsq_selftest_evalguard(const double* d_num, const double* d_den, 
     return FSQ_OK;
 }
 
+// ---- self-test hook: kfit_f32's evaluation (f32_eval of fsq_fit_f32.h: residuals, Jacobian, normal equations) at caller-supplied
+// points.  Pixels are staged as kfit_f32 stages them: 64 lanes per block, pixel k of lane l at pixels[k * 64 + l] ----------------
+namespace {
+__global__ void __launch_bounds__(64) kf32evalcheck(const float* __restrict__ xs, const uint16_t* __restrict__ rois, long long n,
+                                                    float* __restrict__ chi2, float* __restrict__ Nout, float* __restrict__ gout)
+{
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;                             // (no barrier below: a lane only ever reads its own LDS column)
+    __shared__ float pixels[FSQ_NPIX * 64];
+    float* pix = pixels + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < FSQ_NPIX; k++) pix[k * 64] = (float)rois[i * FSQ_NPIX + k];
+    float x[7], N[28], g[7], c2;
+#pragma unroll
+    for (int k = 0; k < 7; k++) x[k] = xs[i * 7 + k];
+    f32_eval(x, pix, c2, N, g);
+    chi2[i] = c2;
+#pragma unroll
+    for (int k = 0; k < 28; k++) Nout[i * 28 + k] = N[k];
+#pragma unroll
+    for (int k = 0; k < 7; k++) gout[i * 7 + k] = g[k];
+}
+}  // namespace
+
+extern "C" int fsq_selftest_f32_eval(const float* d_x, const uint16_t* d_rois, int64_t n, float* d_chi2, float* d_N, float* d_g, void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n < 0 || (n > 0 && (!d_x || !d_rois || !d_chi2 || !d_N || !d_g))) return FSQ_EINVAL;
+    if (n > 0) hipLaunchKernelGGL(kf32evalcheck, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_x, d_rois, (long long)n, d_chi2, d_N, d_g);
+    FSQ_HIP_CHECK(hipGetLastError());
+    return FSQ_OK;
+}
+
 extern "C" int fsq_selftest_exp(const double* d_x, int64_t n, int64_t* mismatches, void* stream)
 {
     hipStream_t s = (hipStream_t)stream;

@@ -327,6 +327,11 @@ int fsq_selftest_rotation(const double* d_t, int64_t n, int64_t* mismatches, voi
 /* fsq_selftest_exp: the fit kernels' branch-free exp (fsq_exp_bf) against the branching restatement of glibc's exp
  * (fsq_exp) - bit equality for |x| < 512; everywhere else (NaN included) the range flag must be raised instead. */
 int fsq_selftest_exp(const double* d_x, int64_t n, int64_t* mismatches, void* stream);
+/* fsq_selftest_f32_eval: the evaluation of the single-precision solver (FSQ_MODE_TEXTBOOK_F32, csrc/fsq_fit_f32.h: f32_eval, the
+ * function its fit kernel calls at every trial point) at n caller-supplied points d_x float[n][7] (H, A, p2, p3, sigma_h, sigma_w,
+ * theta) on n ROIs d_rois uint16[n][25]: d_chi2 float[n] = sum r^2, d_N float[n][28] = J^T J as a packed lower triangle (entry
+ * (i, j), i >= j, at i (i + 1) / 2 + j), d_g float[n][7] = J^T r, r = model - data.  Enqueue only; n == 0 launches nothing. */
+int fsq_selftest_f32_eval(const float* d_x, const uint16_t* d_rois, int64_t n, float* d_chi2, float* d_N, float* d_g, void* stream);
 /* fsq_selftest_square: qrfac's norm down-dating needs libm's pow(t, 2.0) (mpfit.py:1816, a NumPy scalar ** 2); the
  * Jacobian kernel takes t * t wherever that provably is the same number (fsq_square_is_pow2: t^2 further than pow's
  * own error bound from a rounding boundary).  Counts the d_t[i] for which the predicate holds and pow(t, 2.0) != t * t
