@@ -70,7 +70,11 @@ __global__ void __launch_bounds__(256) k6_cross_power(const cplx* __restrict__ F
 
 struct Peak { double re, im; long long idx; };
 __device__ __forceinline__ bool peak_better(const Peak& a, const Peak& b)
-{   // numpy argmax on complex: lexicographic (real, imag); first occurrence wins ties
+{   // numpy argmax on complex: lexicographic (real, imag); first occurrence wins ties; an element with a NaN in either
+    // part beats every number, the first such element wins (one-row / one-column images at upsample_factor > 1: the
+    // upsampled grid is scaled by 1 / (mid_row * mid_col) = 1 / 0, phase_correlate.py:102-111)
+    const bool an = a.re != a.re || a.im != a.im, bn = b.re != b.re || b.im != b.im;
+    if (an || bn) return an && (!bn || a.idx < b.idx);
     if (a.re != b.re) return a.re > b.re;
     if (a.im != b.im) return a.im > b.im;
     return a.idx < b.idx;
@@ -86,8 +90,7 @@ __global__ void __launch_bounds__(256) k6_argmax(const cplx* __restrict__ data, 
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) {
         Peak p;
         p.re = d[i].x * scale; p.im = (conj ? -d[i].y : d[i].y) * scale; p.idx = (long long)i;
-        if (p.re != p.re) continue;                    // NaN never wins (numpy would propagate; inputs are finite)
-        if (peak_better(p, best)) best = p;
+        if (peak_better(p, best)) best = p;            // (a thread visits its elements in rising order: its first NaN stays)
     }
     __shared__ Peak sh[256];
     sh[threadIdx.x] = best;
@@ -497,7 +500,9 @@ RegLayout reg_layout(int n_pairs, int H, int W, int uf, int dtype, bool real_pat
     L.Wh = W / 2 + 1;
     L.up = (int)ceil(uf * 1.5);
     L.Mp = 16 * ((L.up + 15) / 16);
-    L.mfma = (W % 16) == 0 && (H % 4) == 0 && L.Mp <= W && L.Mp <= H;
+    // (FSQ_REGISTER_NO_MFMA is read here, where T and rkT are sized: the vector-ALU DFT expands the whole H x W spectrum
+    // into T, the matrix-core one only keeps Mp x W there)
+    L.mfma = (W % 16) == 0 && (H % 4) == 0 && L.Mp <= W && L.Mp <= H && !getenv("FSQ_REGISTER_NO_MFMA");
     L.parts = 16;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += al(bytes); return at; };
@@ -579,7 +584,7 @@ extern "C" int fsq_phase_correlate(const void* d_ref, const void* d_reg, int dty
     cplx* U = (cplx*)(ws + L.U);
     const int up = L.up, Mp = L.Mp;
     const unsigned pb = (unsigned)((n_pairs + 63) / 64);
-    const bool use_mfma = L.mfma && !getenv("FSQ_REGISTER_NO_MFMA");
+    const bool use_mfma = L.mfma;
     if (hipfftSetWorkArea(fwd.h, ws + L.fftwork) != HIPFFT_SUCCESS) return FSQ_EHIP;
     if (inv.h != fwd.h && hipfftSetWorkArea(inv.h, ws + L.fftwork) != HIPFFT_SUCCESS) return FSQ_EHIP;
     const unsigned blocks = (unsigned)((ntot + 255) / 256);

@@ -53,12 +53,15 @@ static void fft2(const cplx *in, cplx *out, int H, int W, int inverse)
     free(tmp);
 }
 
-/* numpy argmax/max on complex: lexicographic (real, then imag), first occurrence */
+/* numpy argmax/max on complex: lexicographic (real, then imag), first occurrence; the first element with a NaN in
+ * either part wins over everything (the grids of one-row / one-column images, divided by mid_row * mid_col = 0) */
 static size_t cargmax(const cplx *a, size_t n)
 {
     size_t b = 0;
-    for (size_t i = 1; i < n; i++)
+    for (size_t i = 0; i < n; i++) {
+        if (isnan(creal(a[i])) || isnan(cimag(a[i]))) return i;
         if (creal(a[i]) > creal(a[b]) || (creal(a[i]) == creal(a[b]) && cimag(a[i]) > cimag(a[b]))) b = i;
+    }
     return b;
 }
 
