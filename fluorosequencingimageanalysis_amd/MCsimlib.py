@@ -19,6 +19,11 @@ leaves in a trie - for many cycle counts in one launch (project_device, projecti
 SignalTrie.merge does (merge_device, merge_records) and feeds the same compaction, sorts and scan for the whole curve of
 identifiable proteins against cycle count (cycle_curve_records; the command line is proteome_cycles).  SignalTrie.graft,
 prune, merge and truncating_projection are host methods of the drop-in; load_proteome (:55-86) reads a proteome pickle.
+A grid of chemistries over the same peptides: fsq_proteome_signals_points and fsq_proteome_tally_points run every point
+(p, b, u) of a grid in one launch each, one lane per (point, row), into per-point tables (grid_points, grid_device, point_tables,
+grid_records); grid_curve_records gives the identifiable proteins at every point through one compaction, three sorts and one
+scan per group of points (the command line is proteome_sweep).  Row g of point k is sample first_sample + k * sample_stride + g:
+with sample_stride = 0, the default, every point sees the same draws.
 
 ORDER CONTRACTS.  (1) Wherever the reference iterates `windows` - a dict, whose order Python 2 leaves open - this module
 iterates sorted(windows); a signal is a tuple sorted by position, then by acid in that order.  (2) Proteins are scanned in
@@ -474,7 +479,8 @@ def merge_records(a, b, cycles=None, host=False, device=None):
 
 def _sorted_projection(projection):
     """Every cycle count's occupied pairs in one pass, sorted by (cycle index, key as uint64, protein): cycle int64, key int64
-    (bits), protein int32, count int64 and segment int64 [signals + 1] over all cycle counts."""
+    (bits), protein int32, count int64 and segment int64 [signals + 1] over all cycle counts.  Reads any tables with a leading
+    dimension: a grid_device result's just as well, the point's index standing for the cycle index."""
     torch = _engine()._torch()
     t = projection["tables"]
     occupied = t["pairs"] != -1
@@ -517,9 +523,17 @@ def cycle_curve_records(source, worst_ratio, absolute_min, maximum_secondary=Non
         out = H.cycle_curve((source["key"], source["protein"], source["count"]), layout, len(names), cycles, modes, demote)
         out["names"] = names
         return out
+    out = _curve_of_tables(project_device(source, cycles, device=device), len(cycles), len(names), modes, demote)
+    out = dict(cycles=np.array(cycles, np.int64), **out)
+    out["names"] = names
+    return out
+
+
+def _curve_of_tables(stacked, C, P, modes, demote):
+    """The curve's arrays over the C leading tables of `stacked` (a projection's cycle counts, a grid's points) for P proteins:
+    one compaction, three sorts and one fsq_proteome_uniques launch over the concatenated segments."""
     torch = _engine()._torch()
-    C, P = len(cycles), len(names)
-    cyc, _, protein, count, segment = _sorted_projection(project_device(source, cycles, device=device))
+    cyc, _, protein, count, segment = _sorted_projection(stacked)
     got = uniques_device(protein, count, segment, modes, demote)
     dev = cyc.device
     of_signal = cyc[segment[:-1]]
@@ -528,13 +542,231 @@ def cycle_curve_records(source, worst_ratio, absolute_min, maximum_secondary=Non
     identifiable = torch.zeros(C * max(P, 1), dtype=torch.uint8, device=dev)
     identifiable[(of_signal * max(P, 1) + got["best_protein"].to(torch.int64))[passed]] = 1
     identifiable = identifiable.reshape(C, max(P, 1))[:, :P]
-    out = {"cycles": np.array(cycles, np.int64), "n_signals": torch.bincount(of_signal, minlength=C),
+    out = {"n_signals": torch.bincount(of_signal, minlength=C),
            "n_pairs": torch.bincount(cyc, minlength=C), "samples_detected": zeros().index_add_(0, cyc, count),
            "n_passing_signals": zeros().index_add_(0, of_signal, passed.to(torch.int64)),
            "n_identifiable_proteins": identifiable.sum(dim=1, dtype=torch.int64), "identifiable": identifiable.contiguous()}
-    out = {k: v if isinstance(v, np.ndarray) else v.cpu().numpy() for k, v in out.items()}
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+# ---- a grid of (p, b, u) points over the same peptides (fsq_proteome_signals_points, fsq_proteome_tally_points) ----
+
+DEFAULT_TABLE_BYTES = 1 << 33
+
+
+def grid_points(ps, bs, us):
+    """The product of the three axes in p-major order, as a list of (p, b, u): u runs fastest."""
+    return H.grid_points(ps, bs, us)
+
+
+def _check_grid(table, points, sample_size, seed, first_sample, sample_stride):
+    """_check_run for every point under its own first sample: (points as float triples, sample_size, rows per point, stride)."""
+    points = H.check_points(points, sample_stride)
+    stride = int(sample_stride)
+    for k, (p, b, u) in enumerate(points):
+        _, _, _, S, total = _check_run(table, p, b, u, sample_size, seed, int(first_sample) + k * stride)
+    return points, S, total, stride
+
+
+def grid_device_table(table, points, device=None):
+    """device_table for a grid: the peptide table, one Edman table per distinct p (all under the same max_d) and one bleach
+    table per distinct b as CUDA tensors, and `points`, the FsqProteomePoint records (uint8 [n_points][16]) that name them."""
+    torch, NP = _engine()._torch(), _native()
+    dev = torch.device(device or "cuda")
+    max_d = H.max_gap(table)
+    ps, bs, edman_index, bleach_index = H.shared_tables(points)
+    start, values = H.stacked_edman_tables(ps, max_d)
+    records = np.zeros(len(points), np.dtype([("u", "<f8"), ("edman_table", "<i4"), ("bleach_table", "<i4")]))
+    records["u"], records["edman_table"], records["bleach_table"] = [u for _, _, u in points], edman_index, bleach_index
+    assert records.dtype.itemsize == ctypes.sizeof(NP.FsqProteomePoint)
+    up = lambda a: torch.from_numpy(np.array(a)).to(dev)           # (a copy: the cached tables are read-only)
+    return {"protein": up(table["protein"]), "n_head": up(table["n_head"]), "label_start": up(table["label_start"]),
+            "labels": up(np.append(table["labels"], np.uint32(0)).view(np.int32)), "edman_start": up(start),
+            "edman": up(np.append(values, 0.0)), "bleach": up(np.stack([H.bleach_table(b) for b in bs])),
+            "points": up(records.view(np.uint8).reshape(len(points), 16)), "n_edman_tables": len(ps), "n_bleach_tables": len(bs),
+            "max_d": max_d, "n_peptides": len(table["protein"]), "layout": table["layout"], "device": dev}
+
+
+def signals_points_device(gtable, sample_size, seed, first_sample=0, sample_stride=0, first_row=0, n_rows=None, with_draws=False,
+                          first_point=0, n_points=None):
+    """fsq_proteome_signals_points for points first_point .. first_point + n_points - 1 of a grid_device_table (default: all):
+    (key int64 [n_points][n_rows] holding the uint64 keys' bits, protein int32 [n_rows], n_draws int32 [n_points][n_rows] or
+    None).  Row g of the k-th of these points is sample first_sample + k * sample_stride + g.  Enqueued, not synchronised."""
+    torch, NP = _engine()._torch(), _native()
+    layout, dev = gtable["layout"], gtable["device"]
+    lo = int(first_point)
+    K = int(gtable["points"].shape[0]) - lo if n_points is None else int(n_points)
+    if lo < 0 or K < 0 or lo + K > int(gtable["points"].shape[0]):
+        raise ValueError("points beyond the table's %d" % int(gtable["points"].shape[0]))
+    n = gtable["n_peptides"] * int(sample_size) - int(first_row) if n_rows is None else int(n_rows)
+    prm = NP.FsqProteomeParams()
+    for a in range(len(layout.order)):
+        prm.E[a], prm.O[a], prm.base[a] = layout.E[a], layout.O[a], layout.base[a]
+    prm.n_acids, prm.max_d, prm.u = len(layout.order), gtable["max_d"], 0.0
+    prm.seed, prm.first_sample, prm.sample_size = int(seed), int(first_sample), int(sample_size)
+    shape = (max(K, 0), max(n, 0))
+    key = torch.empty(shape, dtype=torch.int64, device=dev)
+    protein = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    draws = torch.empty(shape, dtype=torch.int32, device=dev) if with_draws else None
+    some = n > 0 and K > 0
+    _engine().launch(NP.lib().fsq_proteome_signals_points, "fsq_proteome_signals_points", dev, ctypes.byref(prm),
+                     gtable["points"][lo:].data_ptr() if K > 0 else None, K, int(sample_stride), gtable["protein"].data_ptr(),
+                     gtable["n_head"].data_ptr(), gtable["label_start"].data_ptr(), gtable["labels"].data_ptr(), gtable["n_peptides"],
+                     gtable["edman_start"].data_ptr(), gtable["edman"].data_ptr(), gtable["n_edman_tables"],
+                     gtable["bleach"].data_ptr(), gtable["n_bleach_tables"], int(first_row), n,
+                     key.data_ptr() if some else None, protein.data_ptr() if some else None,
+                     draws.data_ptr() if with_draws and some else None)
+    return key, protein, draws
+
+
+def tally_points_device(tables, d_key, d_protein):
+    """fsq_proteome_tally_points: adds row t of point k (int64 key bits [n_points][n], int32 proteins [n]) to table k of `tables`
+    (new_tables(..., n_masks=n_points)).  Enqueued, not synchronised."""
+    torch, NP = _engine()._torch(), _native()
+    if d_key.dim() != 2 or d_key.dtype != torch.int64 or d_protein.dtype != torch.int32 or tuple(d_protein.shape) != (int(d_key.shape[1]),):
+        raise ValueError("int64 keys [n_points][n] and int32 proteins [n] are needed")
+    K, n = int(d_key.shape[0]), int(d_key.shape[1])
+    if not all(t.is_contiguous() for t in (d_key, d_protein) + tuple(tables.values())):
+        raise ValueError("contiguous tensors are needed")
+    sa, sb = int(tables["signals"].shape[-1]), int(tables["pairs"].shape[-1])
+    if tables["signals"].dim() != 2 or (tables["signals"].numel(), tables["pairs"].numel(), tables["counts"].numel(),
+                                        tables["overflow"].numel()) != (K * sa, K * sb, K * sb, K * 2):
+        raise ValueError("the tables do not hold %d points" % K)
+    _engine().launch(NP.lib().fsq_proteome_tally_points, "fsq_proteome_tally_points", d_key.device, d_key.data_ptr() if n else None,
+                     d_protein.data_ptr() if n else None, K, n, tables["signals"].data_ptr(), sa, tables["pairs"].data_ptr(),
+                     tables["counts"].data_ptr(), sb, tables["overflow"].data_ptr())
+
+
+def check_grid(grid):
+    """Raises ValueError for the first point whose tables were too small."""
+    t = grid["tables"]
+    for i, (a, b) in enumerate(t["overflow"].cpu().tolist()):
+        where = "point %d (p=%r, b=%r, u=%r)" % ((grid.get("first_point", 0) + i,) + tuple(grid["points"][i]))
+        if a:
+            raise ValueError("more distinct signals than signal_slots=%d at %s: pass a larger power of two"
+                             % (int(t["signals"].shape[-1]), where))
+        if b:
+            raise ValueError("more distinct (signal, protein) pairs than pair_slots=%d at %s: pass a larger power of two"
+                             % (int(t["pairs"].shape[-1]), where))
+
+
+def _default_slots(total):
+    return min(max(_pow2_at_least(2 * total), 1024), 1 << 26)
+
+
+def _grid_pass(table, gtable, points, lo, hi, S, total, seed, first_sample, stride, chunk, signal_slots, pair_slots):
+    """Points lo .. hi - 1 of a grid_device_table sampled and tallied into fresh tables: a grid_device result."""
+    K = hi - lo
+    tables = new_tables(signal_slots, pair_slots, gtable["device"], n_masks=K)
+    for first in range(0, total, chunk):
+        key, protein, _ = signals_points_device(gtable, S, seed, first_sample + lo * stride, stride, first, min(chunk, total - first),
+                                                first_point=lo, n_points=K)
+        tally_points_device(tables, key, protein)
+    grid = {"tables": tables, "points": list(points[lo:hi]), "names": table["names"], "layout": table["layout"], "rows": total,
+            "first_point": lo}
+    check_grid(grid)
+    return grid
+
+
+def grid_device(table, points, sample_size, seed, first_sample=0, sample_stride=0, chunk_rows=DEFAULT_CHUNK_ROWS, signal_slots=None,
+                pair_slots=None, device=None):
+    """monte_carlo_device at every point (p, b, u) of `points` in one pass: every peptide of `table` sampled sample_size times a
+    point and counted into that point's own tables, all on the device.  Row g of point k is sample first_sample + k *
+    sample_stride + g: with sample_stride = 0 (the default) every point sees the same draws (common random numbers).  Points with
+    the same p share an Edman table, points with the same b a bleach table; a point may appear twice, each copy gets its tables.
+    A launch covers at most chunk_rows rows of every point (8 bytes of key a point and row) and the result does not depend on
+    it.  Returns a dict: `tables` (new_tables(..., n_masks=len(points)): row i is the tally of points[i]; see
+    point_tables), `points`, `names`, `layout`, `rows` (per point).  signal_slots / pair_slots are per point, by default
+    monte_carlo_device's.  A table that is too small raises ValueError naming its keyword and the first such point."""
+    points, S, total, stride = _check_grid(table, points, sample_size, seed, first_sample, sample_stride)
+    chunk = int(chunk_rows)
+    if chunk < 1:
+        raise ValueError("chunk_rows must be positive")
+    default = _default_slots(total)
+    grid = _grid_pass(table, grid_device_table(table, points, device), points, 0, len(points), S, total, seed, int(first_sample),
+                      stride, chunk, default if signal_slots is None else signal_slots, default if pair_slots is None else pair_slots)
+    del grid["first_point"]
+    return grid
+
+
+def point_tables(grid, i):
+    """The tables of the i-th point of a grid_device result, in the form of a run: pairs_device, uniques_records,
+    cycle_curve_records, project_device and merge_device take it unchanged (the cycle_tables of a grid)."""
+    return {"tables": {k: v[i] for k, v in grid["tables"].items()}, "names": grid["names"], "layout": grid["layout"],
+            "rows": grid["rows"]}
+
+
+def _grid_groups(n_points, total, points_per_pass, table_bytes, signal_slots, pair_slots):
+    default = _default_slots(total)
+    sa, sb = default if signal_slots is None else int(signal_slots), default if pair_slots is None else int(pair_slots)
+    if points_per_pass is None:
+        per = max(int(table_bytes) // (8 * sa + 16 * sb + 8), 1)
+    else:
+        per = int(points_per_pass)
+        if per < 1:
+            raise ValueError("points_per_pass must be positive")
+    per = min(per, _native().MAX_POINTS, n_points)
+    return sa, sb, [(lo, min(lo + per, n_points)) for lo in range(0, n_points, per)]
+
+
+def grid_curve_records(peptides_or_table, points, worst_ratio, absolute_min, maximum_secondary=None, windows=None, sample_size=100,
+                       seed=0, first_sample=0, sample_stride=0, absolute=False, demote=False, points_per_pass=None,
+                       table_bytes=DEFAULT_TABLE_BYTES, host=False, chunk_rows=DEFAULT_CHUNK_ROWS, signal_slots=None, pair_slots=None,
+                       device=None):
+    """Identifiable proteins against the chemistry: the proteome Monte-Carlo and find_uniques' scan (absolute=True:
+    find_uniques_absolute's, absolute_min its minimum_best) at every point (p, b, u) of `points`, what monte_carlo_device +
+    uniques_records + identifiable_proteins give point by point.  `peptides_or_table` is an attached-peptide dict (with `windows`)
+    or a proteome_table; draws as grid_device.  Returns arrays over the points - p, b, u (float64) and the int64 n_signals, n_pairs,
+    samples_detected, n_passing_signals, n_identifiable_proteins - with identifiable uint8 [n_points][n_proteins] (1: best for a
+    passing signal) and names.
+    The points go through the device in groups of points_per_pass; by default as many as table_bytes of tables hold (8 bytes a
+    signal slot, 16 a pair slot, per point), table_bytes by default 2^33 (8 GiB: 85 points at a million samples a point).  A
+    group is one or more fsq_proteome_signals_points + fsq_proteome_tally_points launches, one compaction, three sorts and one
+    fsq_proteome_uniques launch, and is reduced to its rows of the curve before the next group allocates.  The result does not
+    depend on points_per_pass, table_bytes or chunk_rows.  host=True runs the NumPy twins point by point."""
+    table = _as_table(peptides_or_table, windows)
+    points, S, total, stride = _check_grid(table, points, sample_size, seed, first_sample, sample_stride)
+    names = list(table["names"])
+    modes = H.scan_modes(None if absolute else worst_ratio, absolute_min, maximum_secondary, absolute=absolute)
+    if host:
+        proteins = H.row_proteins(table, S, 0, total)
+        triples = (H.tally(H.signals(table, p, b, u, S, seed, int(first_sample) + k * stride)[0], proteins)
+                   for k, (p, b, u) in enumerate(points))
+        out = H.grid_curve(triples, points, len(names), modes, demote)
+        out["names"] = names
+        return out
+    chunk = int(chunk_rows)
+    if chunk < 1:
+        raise ValueError("chunk_rows must be positive")
+    sa, sb, groups = _grid_groups(len(points), total, points_per_pass, table_bytes, signal_slots, pair_slots)
+    gtable = grid_device_table(table, points, device)
+    parts = []
+    for lo, hi in groups:
+        grid = _grid_pass(table, gtable, points, lo, hi, S, total, seed, int(first_sample), stride, chunk, sa, sb)
+        parts.append(_curve_of_tables(grid, hi - lo, len(names), modes, demote))
+        del grid
+    out = {name: np.array([point[j] for point in points], np.float64) for j, name in enumerate("pbu")}
+    out.update({name: np.concatenate([part[name] for part in parts]) for name in parts[0]})
     out["names"] = names
     return out
+
+
+def grid_records(peptides_or_table, points, windows=None, sample_size=100, seed=0, first_sample=0, sample_stride=0,
+                 chunk_rows=DEFAULT_CHUNK_ROWS, signal_slots=None, pair_slots=None, device=None, host=False):
+    """{point: records}, each in the shape of monte_carlo_records, for small grids: all points go through one grid_device pass.
+    Where a point stands twice its last copy is kept."""
+    table = _as_table(peptides_or_table, windows)
+    points, S, total, stride = _check_grid(table, points, sample_size, seed, first_sample, sample_stride)
+    record = lambda k, pr, c: {"key": k, "protein": pr, "count": c, "names": list(table["names"]), "layout": table["layout"]}  # noqa: E731
+    if host:
+        proteins = H.row_proteins(table, S, 0, total)
+        return {point: record(*H.tally(H.signals(table, *point, S, seed, int(first_sample) + k * stride)[0], proteins))
+                for k, point in enumerate(points)}
+    grid = grid_device(table, points, S, seed, first_sample, stride, chunk_rows, signal_slots, pair_slots, device)
+    of_point, key, protein, count, _ = (t.cpu().numpy() for t in _sorted_projection(grid))
+    edges = np.searchsorted(of_point, np.arange(len(points) + 1))
+    return {point: record(key[lo:hi].view(np.uint64), protein[lo:hi], count[lo:hi])
+            for point, lo, hi in zip(points, edges[:-1], edges[1:])}
 
 
 def load_proteome(filename, silent=True):

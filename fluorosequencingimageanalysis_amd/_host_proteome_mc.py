@@ -644,3 +644,83 @@ def cycle_curve(triples, layout, n_proteins, cycles, modes, demote=False):
         out["identifiable"][i, u["best_protein"][u["passed"] != 0]] = 1
     out["n_identifiable_proteins"] = out["identifiable"].sum(axis=1).astype(np.int64)
     return out
+
+
+# ---- a grid of (p, b, u) points (fsq_proteome_signals_points, fsq_proteome_tally_points) ----
+
+MAX_POINTS = 4096                           # FSQ_PMC_MAX_POINTS
+
+
+def grid_points(ps, bs, us):
+    """The product of the three axes in p-major order: [(p, b, u), ...], u running fastest."""
+    return [(float(p), float(b), float(u)) for p in ps for b in bs for u in us]
+
+
+def check_points(points, sample_stride=0):
+    """The points as a list of float triples; raises for none, for more than MAX_POINTS, for a p or u outside [0, 1], a negative
+    b or a negative stride."""
+    points = [tuple(float(v) for v in point) for point in points]
+    if not points:
+        raise ValueError("no point")
+    if len(points) > MAX_POINTS:
+        raise ValueError("%d points; at most %d" % (len(points), MAX_POINTS))
+    for i, point in enumerate(points):
+        if len(point) != 3:
+            raise ValueError("point %d is not (p, b, u)" % i)
+        p, b, u = point
+        if not (0.0 <= p <= 1.0 and 0.0 <= u <= 1.0 and b >= 0.0):
+            raise ValueError("point %d (p=%r, b=%r, u=%r): p and u must be in [0, 1] and b must not be negative" % (i, p, b, u))
+    if int(sample_stride) != sample_stride or sample_stride < 0:
+        raise ValueError("sample_stride must be a non-negative integer")
+    return points
+
+
+def shared_tables(points):
+    """The distinct p and b values of the points in first-seen order, and per point the index of its value: (ps, bs,
+    edman_index int32 [n], bleach_index int32 [n]).  The same float gives the same table."""
+    ps, bs = {}, {}
+    edman = [ps.setdefault(p, len(ps)) for p, _, _ in points]
+    bleach = [bs.setdefault(b, len(bs)) for _, b, _ in points]
+    return list(ps), list(bs), np.array(edman, np.int32), np.array(bleach, np.int32)
+
+
+def stacked_edman_tables(ps, max_d):
+    """edman_table of every p under the same max_d as one array: (start int64 [len(ps)][max_d + 2], offsets into values;
+    values float64)."""
+    starts, values, at = [], [], 0
+    for p in ps:
+        start, v = edman_table(p, max_d)
+        starts.append(start + at)
+        values.append(v)
+        at += len(v)
+    return np.array(starts, np.int64).reshape(len(ps), max_d + 2), np.concatenate(values) if values else np.zeros(0, np.float64)
+
+
+def grid_signals(table, points, sample_size, seed, first_sample=0, sample_stride=0, first_row=0, n_rows=None):
+    """signals for every point: (keys uint64 [n_points][n_rows], n_draws int32 [n_points][n_rows]); row g of point k is sample
+    first_sample + k * sample_stride + g.  The loop of the single-point twin."""
+    points = check_points(points, sample_stride)
+    got = [signals(table, p, b, u, sample_size, seed, first_sample + k * int(sample_stride), first_row, n_rows)
+           for k, (p, b, u) in enumerate(points)]
+    return np.stack([k for k, _ in got]), np.stack([d for _, d in got])
+
+
+def grid_tally(keys, proteins):
+    """tally of every point's row of keys [n_points][n_rows] against the rows' proteins [n_rows]: a list of sorted triples."""
+    return [tally(row, proteins) for row in np.asarray(keys, np.uint64)]
+
+
+def grid_curve(triples_of_point, points, n_proteins, modes, demote=False):
+    """The scan of find_uniques at every point: float64 arrays p, b, u and int64 arrays named as CURVE_FIELDS over the points,
+    and identifiable uint8 [n_points][n_proteins], 1 where the protein is best for a passing signal."""
+    out = {name: np.zeros(len(points), np.int64) for name in CURVE_FIELDS}
+    for j, name in enumerate("pbu"):
+        out[name] = np.array([point[j] for point in points], np.float64)
+    out["identifiable"] = np.zeros((len(points), int(n_proteins)), np.uint8)
+    for i, t in enumerate(triples_of_point):
+        u = _uniques(t, modes, demote)
+        out["n_signals"][i], out["n_pairs"][i], out["samples_detected"][i] = len(u["key"]), len(t[0]), t[2].sum()
+        out["n_passing_signals"][i] = np.count_nonzero(u["passed"])
+        out["identifiable"][i, u["best_protein"][u["passed"] != 0]] = 1
+    out["n_identifiable_proteins"] = out["identifiable"].sum(axis=1).astype(np.int64)
+    return out

@@ -16,6 +16,7 @@ BLOCK, MAX_BLOCKS = 256, 2048       # kpm_signals' and kpm_tally's grid: one pas
 RATIO_NONE, RATIO_NUMBER, RATIO_ABSENT = 0, 1, 2        # FSQ_PMC_RATIO_*
 PROJECT, WITHIN, MASK_MAJOR = 0, 1, 0x100               # FSQ_PMC_PROJECT, FSQ_PMC_WITHIN, FSQ_PMC_MASK_MAJOR
 MAX_MASKS = 4096                    # FSQ_PMC_MAX_MASKS
+MAX_POINTS = 4096                   # FSQ_PMC_MAX_POINTS
 
 
 class FsqProteomeParams(ctypes.Structure):
@@ -30,7 +31,11 @@ class FsqUniquesParams(ctypes.Structure):
                 ("reserved_", ctypes.c_int32)]
 
 
-assert ctypes.sizeof(FsqProteomeParams) == 200 and ctypes.sizeof(FsqUniquesParams) == 40
+class FsqProteomePoint(ctypes.Structure):
+    _fields_ = [("u", ctypes.c_double), ("edman_table", ctypes.c_int32), ("bleach_table", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FsqProteomeParams) == 200 and ctypes.sizeof(FsqUniquesParams) == 40 and ctypes.sizeof(FsqProteomePoint) == 16
 
 _P, _I64 = ctypes.c_void_p, ctypes.c_int64
 _SIGS = {
@@ -38,6 +43,9 @@ _SIGS = {
                                             _P]),
     "fsq_proteome_tally": (ctypes.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P]),
     "fsq_proteome_project": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, ctypes.c_int32, _P, _I64, _P, _P, _I64, _P, _P]),
+    "fsq_proteome_signals_points": (ctypes.c_int, [ctypes.POINTER(FsqProteomeParams), _P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P,
+                                                   ctypes.c_int32, _P, ctypes.c_int32, _I64, _I64, _P, _P, _P, _P]),
+    "fsq_proteome_tally_points": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P]),
     "fsq_proteome_uniques": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(FsqUniquesParams), _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTED = tuple(_SIGS)

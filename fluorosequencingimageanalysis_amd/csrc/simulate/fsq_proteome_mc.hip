@@ -1,6 +1,7 @@
 // fsq_proteome_mc.hip - the proteome-scale Monte-Carlo of MCsimlib.py (C ABI of include/fsq_proteome_mc.h).
 //
-//   kpm_signals   one lane per sample of the flattened [peptides][sample_size] space: random_signal (:863-1074) as a 64-bit key.
+//   kpm_signals   one lane per sample of the flattened [peptides][sample_size] space: random_signal (:863-1074) as a 64-bit key
+//                 (the per-sample body is pmc_sample of fsq_proteome_lane.h, which fsq_proteome_points.hip shares).
 //                 Pass 1 compares the dud draws with u and builds the survivor mask; pass 2 walks the survivors.  The Edman
 //                 delay is a binary search in the host-built row of running _dp sums, the bleach a binary search in the
 //                 host-built survival table: no exp, no pow, no per-lane arrays.  A peptide's labels are read straight from
@@ -13,53 +14,13 @@
 #include "../fsq_common.h"
 #include "../fsq_devmath.h"
 #include "../../../include/fsq_proteome_mc.h"
-#include "fsq_philox.h"
+#include "fsq_proteome_lane.h"
 #include "fsq_pmc_insert.h"
 
 namespace {
 
 constexpr int PMC_BLOCK = 256;
 constexpr int PMC_MAX_BLOCKS = 2048;            // one pass of kpm_signals / kpm_tally covers 524 288 rows
-
-// the draws of one item's stream 3, random access; the last block is kept
-struct ItemDraws {
-    uint32_t lo, hi, k0, k1;
-    int block;
-    Words w;
-    __device__ __forceinline__ double get(const int j)
-    {
-        const int b = j >> 1;
-        if (b != block) {
-            w = philox4x32_10((uint32_t)b, lo, hi, (uint32_t)FSQ_PMC_STREAM, k0, k1);
-            block = b;
-        }
-        return (j & 1) ? uniform53(w.w2, w.w3) : uniform53(w.w0, w.w1);
-    }
-};
-
-// the first i < n with row[i] >= r, else n; n <= 4096
-__device__ __forceinline__ int first_at_least(const double* __restrict__ row, int n, const double r)
-{
-    int lo = 0;
-    for (int it = 0; it < 13 && n > 0; ++it) {
-        const int half = n >> 1;
-        if (row[lo + half] < r) { lo += half + 1; n -= half + 1; }
-        else n = half;
-    }
-    return lo;
-}
-
-// the position of set bit number s (0-based) of m; m has more than s set bits
-__device__ __forceinline__ int nth_set_bit(unsigned long long m, int s)
-{
-    int pos = 0;
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) {
-        const int c = __builtin_popcountll(m & ((1ull << w) - 1ull));
-        if (s >= c) { s -= c; m >>= w; pos += w; }
-    }
-    return pos;
-}
 
 __global__ void __launch_bounds__(PMC_BLOCK)
 kpm_signals(const FsqProteomeParams prm, const int32_t* __restrict__ g_protein, const int32_t* __restrict__ g_n_head,
@@ -85,63 +46,13 @@ kpm_signals(const FsqProteomeParams prm, const int32_t* __restrict__ g_protein, 
         const long long g = first_row + t;
         const long long pep = g / prm.sample_size;
         const unsigned long long item = prm.first_sample + (unsigned long long)g;
-        const long long ls = g_label_start[pep];
-        int L = (int)(g_label_start[pep + 1] - ls);
-        L = L < 0 ? 0 : L > FSQ_PMC_MAX_LABELS ? FSQ_PMC_MAX_LABELS : L;
-        int H = g_n_head[pep];
-        H = H < 0 ? 0 : H > L ? L : H;
-        const uint32_t* __restrict__ lab = g_labels + ls;
-        ItemDraws da = {(uint32_t)item, (uint32_t)(item >> 32), (uint32_t)prm.seed, (uint32_t)(prm.seed >> 32), -1, {0, 0, 0, 0}};
-        ItemDraws db = da;
-
-        unsigned long long surv = 0ull;                                             // pass 1: duds (:910-933)
-        for (int j = 0; j < L; ++j)
-            if (da.get(j) > prm.u) surv |= 1ull << ((lab[j] >> 24) & 63u);
-        const int nsh = __builtin_popcountll(surv & (H >= 64 ? ~0ull : (1ull << H) - 1ull));
-
-        unsigned long long key = 0ull;
-        long long cum = 0;
-        int prev = 0, rank = 0;
-        for (int k = 0; k < H; ++k) {                                               // pass 2: surviving head labels by position
-            if (!((surv >> k) & 1ull)) continue;
-            const uint32_t w = lab[k];
-            const int x0 = (int)(w & 0xffu), a = (int)((w >> 8) & 7u);
-            const int d = x0 - prev;
-            prev = x0;
-            const double r = da.get(L + rank);                                      // Edman delay (:960-995)
-            if (d >= 1 && d <= prm.max_d) {
-                const long long at = g_edman_start[d];
-                long long n = g_edman_start[d + 1] - at;
-                n = n < 0 ? 0 : n > FSQ_PMC_MAX_ROW ? FSQ_PMC_MAX_ROW : n;
-                cum += first_at_least(g_edman + at, (int)n, r);
-            }
-            const long long gap = x0 + cum;
-            const double r2 = db.get(L + nsh + rank);                               // bleach (:1007-1040)
-            const unsigned long long Ea = s_E[a], Oa = s_O[a];
-            const long long gm = gap - 1;
-            const unsigned long long expo = gm >= 64 ? Ea : gm <= 0 ? 0ull : Ea & ((1ull << gm) - 1ull);
-            const int s = first_at_least(s_T, FSQ_PMC_MAX_EXPOSURES, r2);
-            long long x = gap;
-            if (s < __builtin_popcountll(expo)) x = nth_set_bit(expo, s) + 1;
-            if (x < 64 && ((Oa >> x) & 1ull)) key |= 1ull << (s_base[a] + __builtin_popcountll(Oa & ((1ull << x) - 1ull)));
-            ++rank;
-        }
-        int trank = 0;
-        for (int k = H; k < L; ++k) {                                               // surviving tail labels (:1044-1056)
-            if (!((surv >> k) & 1ull)) continue;
-            const int a = (int)((lab[k] >> 8) & 7u);
-            const double r = db.get(L + 2 * nsh + trank);
-            const unsigned long long Ea = s_E[a], Oa = s_O[a];
-            const int s = first_at_least(s_T, FSQ_PMC_MAX_EXPOSURES, r);
-            if (s < __builtin_popcountll(Ea)) {
-                const int x = nth_set_bit(Ea, s) + 1;
-                if (x < 64 && ((Oa >> x) & 1ull)) key |= 1ull << (s_base[a] + __builtin_popcountll(Oa & ((1ull << x) - 1ull)));
-            }
-            ++trank;
-        }
+        int L, H, n_draws;
+        const uint32_t* __restrict__ lab = pmc_labels(g_label_start, g_labels, g_n_head, pep, L, H);
+        const unsigned long long key = pmc_sample(item, prm.seed, prm.u, prm.max_d, lab, L, H, g_edman_start, g_edman, s_T, s_E, s_O,
+                                                  s_base, n_draws);
         g_key[t] = key;
         if (g_row_protein) g_row_protein[t] = g_protein[pep];
-        if (g_n_draws) g_n_draws[t] = L + 2 * nsh + trank;
+        if (g_n_draws) g_n_draws[t] = n_draws;
     }
 }
 

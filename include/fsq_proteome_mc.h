@@ -130,6 +130,53 @@ int fsq_proteome_uniques(const int32_t* d_protein, const int64_t* d_count, const
                          const FsqUniquesParams* prm, int32_t* d_best_protein, int64_t* d_best_count, int32_t* d_second_protein,
                          int64_t* d_second_count, int32_t* d_n_ties, int64_t* d_tertiary, uint8_t* d_passed, void* stream);
 
+/* ---- a grid of (p, b, u) points over the same peptides (csrc/simulate/fsq_proteome_points.hip) ---- */
+
+#define FSQ_PMC_MAX_POINTS 4096
+
+typedef struct {
+    double u;                               /* in place of FsqProteomeParams.u */
+    int32_t edman_table;                    /* the point's p: a table of d_edman_start, 0 .. n_edman_tables - 1 */
+    int32_t bleach_table;                   /* the point's b: a table of d_bleach, 0 .. n_bleach_tables - 1 */
+} FsqProteomePoint;
+
+/* fsq_proteome_signals for n_points points at once, one lane per (point, row): rows first_row .. first_row + n_rows - 1 of the
+ * [n_peptides][sample_size] space, the same for every point.  Row g of point k is sample base->first_sample + k * sample_stride
+ * + g, reads stream 3 of that item under base->seed and uses d_points[k].u, Edman table d_points[k].edman_table and bleach table
+ * d_points[k].bleach_table in place of base->u (which is not read) and the single tables.  sample_stride = 0: every point sees
+ * the same draws (common random numbers).  d_key[k][t] and d_n_draws[k][t] are what fsq_proteome_signals writes for that sample
+ * under that point's parameters, bit for bit: both kernels run the same per-sample body (csrc/simulate/fsq_proteome_lane.h).
+ *   d_points       FsqProteomePoint [n_points]
+ *   the peptide table (d_protein .. n_peptides) as fsq_proteome_signals takes it
+ *   d_edman_start  int64  [n_edman_tables][max_d + 2]  offsets into d_edman: row d of table e is d_edman[start[e][d] ..
+ *                  start[e][d + 1]); all tables are built with the same base->max_d
+ *   d_bleach       double [n_bleach_tables][FSQ_PMC_MAX_EXPOSURES]
+ *   d_key          uint64 [n_points][n_rows]
+ *   d_row_protein  int32  [n_rows] or null   the row's protein (the same for every point)
+ *   d_n_draws      int32  [n_points][n_rows] or null
+ * A point's table indices are device data the entry cannot check: the kernel clamps them into 0 .. n_tables - 1, so a wrong
+ * index gives wrong keys and never a read outside the tables.  n_points outside 1 .. FSQ_PMC_MAX_POINTS, a negative
+ * sample_stride, sample ids beyond 2^64 - 1, fewer than one table of a kind, n_points * n_rows beyond int64, null pointers
+ * (d_row_protein and d_n_draws aside) and what fsq_proteome_signals refuses return FSQ_EINVAL and write nothing; n_rows == 0
+ * returns FSQ_OK. */
+int fsq_proteome_signals_points(const FsqProteomeParams* base, const FsqProteomePoint* d_points, int64_t n_points,
+                                int64_t sample_stride, const int32_t* d_protein, const int32_t* d_n_head,
+                                const int64_t* d_label_start, const uint32_t* d_labels, int64_t n_peptides,
+                                const int64_t* d_edman_start, const double* d_edman, int32_t n_edman_tables, const double* d_bleach,
+                                int32_t n_bleach_tables, int64_t first_row, int64_t n_rows, uint64_t* d_key, int32_t* d_row_protein,
+                                int32_t* d_n_draws, void* stream);
+
+/* fsq_proteome_tally for n_points points at once, one lane per (point, row): element t of point k (d_key[k][t], d_row_protein[t])
+ * goes into table k of d_signals [n_points][signal_slots], d_pairs / d_counts [n_points][pair_slots], d_overflow [n_points][2].
+ * Table k has the slot format of fsq_proteome_tally and is prepared as there; calls accumulate, and fsq_proteome_tally and
+ * fsq_proteome_project read and extend a point's tables as they are.  A full table of point k sets d_overflow[k][0] (signals) or
+ * [k][1] (pairs), loses that row and leaves every other point exact.  With n_points = 1 the (key, count) sets are
+ * fsq_proteome_tally's.  n_points outside 1 .. FSQ_PMC_MAX_POINTS, slot counts that are no power of two within the limits above,
+ * n_points * n_rows beyond int64 and null pointers return FSQ_EINVAL and write nothing; n_rows == 0 returns FSQ_OK. */
+int fsq_proteome_tally_points(const uint64_t* d_key, const int32_t* d_row_protein, int64_t n_points, int64_t n_rows,
+                              uint64_t* d_signals, int64_t signal_slots, uint64_t* d_pairs, int64_t* d_counts, int64_t pair_slots,
+                              int32_t* d_overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
