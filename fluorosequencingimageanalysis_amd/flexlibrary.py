@@ -162,7 +162,9 @@ class Spot(object):
         self.gaussian_fit = gaussian_fit
 
     def image_slice(self, radius=None):
-        """The Spot's square of pixels, clipped at the image borders.  flexlibrary.py:113-146."""
+        """The Spot's square of pixels as numpy slices it: clipped at the borders, except that a centre more than `radius`
+        beyond row or column 0 gives a negative stop, which numpy counts from the far end (a wrapped window, as in the
+        reference).  flexlibrary.py:113-146."""
         if radius is None:
             radius = (self.size - 1) // 2
         img = self.parent_Image.image
@@ -183,7 +185,7 @@ class Spot(object):
         return np.sum(self.image_slice())
 
     def mexican_hat_photometry_metric(self, brim_size=6, radius=9, return_invalid=True):
-        """sum(crown) - len(crown) * median(brim) over the clipped (2 radius + 1)^2 window.  flexlibrary.py:172-210
+        """sum(crown) - len(crown) * median(brim) over image_slice(radius), wrapped windows included.  flexlibrary.py:172-210
         (one spot through fsq_mexican_hat; photometry.mexican_hat_photometry_metric takes whole tables)."""
         from . import photometry as _ph
         if radius is None:

@@ -12,8 +12,11 @@ def mexican_hat_photometry_metric(images, spots, brim_size=6, radius=9):
 
     images: one 2-D integer image or a stack [n_fields, H, W] (values in [0, 2^31); beyond 65 535: fsq_mexican_hat_u32);
     spots:  int array [n, 2] of (h, w) centres for a single image, or [n, 3] of (field, h, w) for a stack.
-    Returns float64[n]: sum(crown pixels) - len(crown) * median(brim pixels) over the (2*radius+1)^2 window, clipped at the
-    image borders exactly as Spot.image_slice does (return_invalid=True behaviour)."""
+    Returns float64[n]: sum(crown pixels) - len(crown) * median(brim pixels) over the (2*radius+1)^2 window as
+    Spot.image_slice cuts it out (return_invalid=True behaviour): image[max(0, c - radius):min(n, c + radius + 1)] per axis
+    under numpy's slice rules.  Beyond the far border and at the near one the window is clipped; a centre more than `radius`
+    beyond row or column 0 makes the stop negative, which numpy counts from the far end, so such a spot measures a wrapped
+    window of up to n - 1 rows or columns (empty, and the result NaN, only below -n - radius), as in the reference."""
     torch = _engine._torch()
     imgs, fmt = _engine.as_integer_fields(images)
     if imgs.ndim == 2:

@@ -248,8 +248,10 @@ int fsq_phase_correlate(const void* d_ref, const void* d_reg, int dtype, int n_p
 /*
  * Spot photometry on the peak table: Spot.mexican_hat_photometry_metric, flexlibrary.py:172-210.
  *   d_img   uint16[n_fields][H][W]; d_fhw int32[n][3] = (field, h, w) integer spot centres (the caller guarantees
- *           0 <= field < n_fields; h, w may lie anywhere - the window is clipped like Spot.image_slice,
- *           flexlibrary.py:140-146, and an empty brim gives nan like numpy.median([]))
+ *           0 <= field < n_fields; h, w may lie anywhere - the window is cut out like Spot.image_slice,
+ *           flexlibrary.py:140-146, under numpy's slice rules: clipped at the borders, but a centre more than `radius`
+ *           beyond row or column 0 makes the stop negative, which counts from the far end (a wrapped window of up to
+ *           n - 1 rows or columns); an empty brim gives nan like numpy.median([]))
  *   d_out   double[n]: sum(crown) - len(crown) * median(brim); any radius (windows beyond 31 x 31 are re-read per median step)
  * Enqueues on the stream, does not synchronise.
  */

@@ -895,18 +895,28 @@ double fsq_o_numpy_sum(const double *a, long n) { return numpy_sum(a, (size_t)n)
 
 
 /* ---- Spot photometry -----------------------------------------------------------------------------
- * Spot.mexican_hat_photometry_metric, flexlibrary.py:172-210: the (2*radius+1)^2 window around (h, w), clipped at the
- * image borders by image_slice (flexlibrary.py:140-146); in the coordinates of the CLIPPED slice a pixel belongs to
+ * Spot.mexican_hat_photometry_metric, flexlibrary.py:172-210: the (2*radius+1)^2 window around (h, w) as image_slice cuts
+ * it out (flexlibrary.py:140-146): image[max(0, c - r) : min(n, c + r + 1)] per axis under numpy's slice rules, so a stop below
+ * zero counts from the far end (a spot more than its radius beyond row or column 0 gets a wrapped window of up to n - 1 rows or
+ * columns), and the window is empty when stop <= start; in the coordinates of THAT slice a pixel belongs to
  * the crown when brim <= row < diameter - brim and the same for the column, to the brim otherwise;
  * photometry = sum(crown) - len(crown) * numpy.median(brim).  Pixels are integers, so everything is exact:
  * the median of an even count is the mean of the two middle values, of an empty brim nan. */
+static void hat_axis(int c, int r, int n, int *start, int *stop)
+{
+    long long s = (long long)c - r < 0 ? 0 : (long long)c - r, e = (long long)c + r + 1 > n ? n : (long long)c + r + 1;
+    if (e < 0) { e += n; if (e < 0) e = 0; }
+    if (e < s) e = s;
+    *start = (int)(s > n ? n : s); *stop = (int)(s > n ? n : e);
+}
 static double mexican_hat_any(const void *img, int wide, int H, int W, int h, int w, int brim, int radius)
 {
-    int r0 = h - radius < 0 ? 0 : h - radius, r1 = h + radius + 1 > H ? H : h + radius + 1;
-    int c0 = w - radius < 0 ? 0 : w - radius, c1 = w + radius + 1 > W ? W : w + radius + 1;
+    int r0, r1, c0, c1;
+    hat_axis(h, radius, H, &r0, &r1);
+    hat_axis(w, radius, W, &c0, &c1);
     int diameter = 2 * radius + 1;
     long long crown = 0, ncrown = 0;
-    int nb = 0, cap = (r1 > r0 && c1 > c0) ? (r1 - r0) * (c1 - c0) : 0;
+    size_t nb = 0, cap = (r1 > r0 && c1 > c0) ? (size_t)(r1 - r0) * (size_t)(c1 - c0) : 0;
     int64_t *b = (int64_t *)malloc((cap > 0 ? cap : 1) * sizeof(int64_t));
     for (int r = r0; r < r1; r++)
         for (int c = c0; c < c1; c++) {
