@@ -145,6 +145,12 @@ def detect_params(median_filter_size, correlation_matrix, c_std, pixel_format=N.
         raise ValueError("correlation_matrix must be square, with an odd number of rows and columns")
     if K.shape[0] > N.MAX_KSIZE or not (1 <= int(median_filter_size) <= N.MAX_KSIZE):
         raise NotImplementedError("correlation_matrix / median_filter_size larger than %d are not supported" % N.MAX_KSIZE)
+    if K.dtype.kind not in "iub":
+        # The reference correlates a floating-point matrix in floating point (scipy picks the FFT method) and truncates the
+        # RESPONSE; truncating the matrix instead gives other candidates, and even an integral-valued float matrix does not
+        # reproduce the integer matrix's threshold there.
+        raise NotImplementedError("the GPU path takes integer correlation matrices only (got dtype %s): the reference correlates "
+                                  "other matrices in floating point" % K.dtype)
     p = N.FsqDetectParams()
     p.median_filter_size = int(median_filter_size)
     p.ksz = int(K.shape[0])
