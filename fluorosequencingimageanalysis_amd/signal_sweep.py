@@ -515,8 +515,8 @@ def joint_signals_of_fits(letters, best_seq, found, category, host=False, table_
     """The observed side of a joint sweep: {joint_signal: n} of row-aligned per-channel lognormal fits of the same tracks.
     best_seq uint8 [K][n][F], found and category [K][n] (non-zero: the channel's fit was found; the channel is lit), NumPy
     arrays or tensors, the channels in sorted-letter order.  A track counts when it has a lit channel and every lit channel was
-    found; a dark channel counts as a row of zeros.  Through fsq_signal_tally_joint, or the twin with host=True.  Aligning a
-    two-channel track table by track is the caller's."""
+    found; a dark channel counts as a row of zeros.  Through fsq_signal_tally_joint, or the twin with host=True.  From a
+    two-channel track table: colocalize.joint_observed_records, which aligns the channels' tracks and calls this."""
     letters = tuple(letters)
     if host:
         best, found, category = (np.asarray(x.cpu() if hasattr(x, "cpu") else x) for x in (best_seq, found, category))

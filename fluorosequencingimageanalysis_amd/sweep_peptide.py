@@ -18,7 +18,8 @@ the observed total and the twelve heat-map tables), and prints the number of exc
 needs --heatmap_normalize_counts, or --all_signals with --normalize_counts.  --host runs the NumPy twins; no GPU needed.
 
 Several label letters (LABEL "KC", up to 4, one colour channel each) run signal_sweep's joint path: SIGNALS.pkl then holds
-{(decrements, zeros, starts): count} of joint signals (signal_sweep.joint_signals_of_fits makes one), --fluor_intensity,
+{(decrements, zeros, starts): count} of joint signals (python -m fluorosequencingimageanalysis_amd.joint_signals writes one
+from a two-channel track table; signal_sweep.joint_signals_of_fits makes one from aligned fits), --fluor_intensity,
 --beta_sigma, --superdye_rate and --superdye_factor take one number or K=..,C=.., and the pickle gains `labels`, the sorted
 letters; `diagnostic` then has no heat-map tables.  One letter runs and writes what it did before."""
 import argparse
