@@ -26,6 +26,11 @@ namespace {
 
 __device__ __forceinline__ double round_key(double x, int py2) { return py2 ? round(x) : rint(x); }
 
+// key_h of a row that is not alive at the re-key (filtered, or deleted by the consolidation).  An entry that IS alive gets its rounded
+// centre there, and a centre may round to a negative row - the reference keeps such an entry under the key (-1, w) - so "alive" cannot
+// be `key_h >= 0`: the mark is a value that no centre of magnitude below 2^31 rounds to (include/fsq.h).
+constexpr int K5_DEAD = -2147483647 - 1;
+
 // loads / stores other waves of the block act upon while this one runs: atomic at WORKGROUP scope - all waves of a block sit on
 // one CU and share its vector L1, so nothing has to leave the CU (agent-scope fences write back and invalidate the whole L2
 // of the XCD on gfx950: tried first, 50 ms per launch)
@@ -96,7 +101,7 @@ __global__ void __launch_bounds__(1024) k5_consolidate(FsqRow* __restrict__ rows
     // then touch ~15 % of the candidates.
     int* surv = keep + off;
     for (int i = tid; i < cnt; i += blockDim.x) {
-        R[i].key_h = -1; R[i].key_w = -1;
+        R[i].key_h = K5_DEAD; R[i].key_w = -1;
         if (!(R[i].r2 < r2_thr)) { grid[(size_t)R[i].h * W + R[i].w] = i; turn[i] = 0; }
     }
     __syncthreads();
@@ -284,7 +289,7 @@ __global__ void __launch_bounds__(1024) k5_consolidate(FsqRow* __restrict__ rows
     __syncthreads();
     for (int s_ = tid; s_ < nsurv; s_ += blockDim.x) {
         const int i = surv[s_];
-        if (R[i].key_h >= 0 && (R[i].key_h != R[i].h || R[i].key_w != R[i].w)) grid[(size_t)R[i].h * W + R[i].w] = -1;
+        if (R[i].key_h != K5_DEAD && (R[i].key_h != R[i].h || R[i].key_w != R[i].w)) grid[(size_t)R[i].h * W + R[i].w] = -1;
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
@@ -297,9 +302,9 @@ __global__ void __launch_bounds__(1024) k5_consolidate(FsqRow* __restrict__ rows
     __syncthreads();
 
     // kept list in the reference's dict order: untouched keys in insertion order, re-keyed ones appended
-    const int nk0 = block_compact(cnt, chunkc, keep, off, [&](int i) { return R[i].key_h >= 0 && R[i].key_h == R[i].h && R[i].key_w == R[i].w; },
+    const int nk0 = block_compact(cnt, chunkc, keep, off, [&](int i) { return R[i].key_h != K5_DEAD && R[i].key_h == R[i].h && R[i].key_w == R[i].w; },
                                   [&](int i) { return off + i; }, &s_total);
-    const int nk1 = block_compact(cnt, chunkc, keep, off + nk0, [&](int i) { return R[i].key_h >= 0 && (R[i].key_h != R[i].h || R[i].key_w != R[i].w); },
+    const int nk1 = block_compact(cnt, chunkc, keep, off + nk0, [&](int i) { return R[i].key_h != K5_DEAD && (R[i].key_h != R[i].h || R[i].key_w != R[i].w); },
                                   [&](int i) { return off + i; }, &s_total);
     if (tid == 0) nkeep[f] = s_assert ? -1 : nk0 + nk1;
 }
@@ -369,7 +374,7 @@ __global__ void __launch_bounds__(64) k5c_insert(FsqRow* __restrict__ rows, cons
 {
     const K5Field F = k5_field(rows, counts, offsets, blockIdx.y, H, W, ws, stride);
     for (int i = blockIdx.x * 64 + threadIdx.x; i < F.cnt; i += gridDim.x * 64) {
-        F.R[i].key_h = -1; F.R[i].key_w = -1;
+        F.R[i].key_h = K5_DEAD; F.R[i].key_w = -1;
         const bool surv = !(F.R[i].r2 < r2_thr);
         F.parent[i] = surv ? i : -1;
         F.last[i] = i;
@@ -538,7 +543,7 @@ __global__ void __launch_bounds__(512) k5c_finish(FsqRow* __restrict__ rows, con
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     for (int i = tid; i < cnt; i += blockDim.x)
-        if (R[i].key_h >= 0 && (R[i].key_h != R[i].h || R[i].key_w != R[i].w)) grid[(size_t)R[i].h * W + R[i].w] = -1;
+        if (R[i].key_h != K5_DEAD && (R[i].key_h != R[i].h || R[i].key_w != R[i].w)) grid[(size_t)R[i].h * W + R[i].w] = -1;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     for (int i = tid; i < cnt; i += blockDim.x) {
@@ -548,9 +553,9 @@ __global__ void __launch_bounds__(512) k5c_finish(FsqRow* __restrict__ rows, con
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
-    const int nk0 = block_compact(cnt, chunkc, keep, off, [&](int i) { return R[i].key_h >= 0 && R[i].key_h == R[i].h && R[i].key_w == R[i].w; },
+    const int nk0 = block_compact(cnt, chunkc, keep, off, [&](int i) { return R[i].key_h != K5_DEAD && R[i].key_h == R[i].h && R[i].key_w == R[i].w; },
                                   [&](int i) { return off + i; }, &s_total);
-    const int nk1 = block_compact(cnt, chunkc, keep, off + nk0, [&](int i) { return R[i].key_h >= 0 && (R[i].key_h != R[i].h || R[i].key_w != R[i].w); },
+    const int nk1 = block_compact(cnt, chunkc, keep, off + nk0, [&](int i) { return R[i].key_h != K5_DEAD && (R[i].key_h != R[i].h || R[i].key_w != R[i].w); },
                                   [&](int i) { return off + i; }, &s_total);
     if (tid == 0) nkeep[f] = s_assert ? -1 : nk0 + nk1;
 }

@@ -179,7 +179,25 @@ int64_t fsq_consolidate_workspace_bytes(int n_fields, int H, int W);
  *              d_keep[offsets[f] .. offsets[f] + nkeep[f]), in the reference's dict order
  *   d_nkeep    int32[n_fields+1] out: kept per field, [n_fields] = total; -1 for a field whose
  *              re-key assertion (pflib.py:518) fired
- * key_h/key_w of the kept rows are filled in.
+ * key_h/key_w of the kept rows are filled in.  Nothing else of d_rows is written.
+ *
+ * What the call takes for granted and what it leaves behind (tests/test_gpu_consolidate_limits.py pins what is stated here):
+ *   - 2 <= h < H - 2 and 2 <= w < W - 2 is not required, 0 <= h < H and 0 <= w < W is; (h, w) must be unique within a field
+ *     (the reference's setdefault would keep the first of two rows with one pixel, the kernel's insertion the last writer's;
+ *     fsq_detect never emits two).
+ *   - A kept row's key is its rounded centre wherever that lies: an entry whose centre rounds to a row or column outside the
+ *     frame - a negative one included - is kept under that key, as the reference's dict keeps it.  Centres must be below 2^31 in
+ *     magnitude.
+ *   - In a field that has a table (nkeep >= 0), a row that is not kept holds key_h = INT32_MIN, key_w = -1.  In a field whose
+ *     assertion fired the keys are unspecified.
+ *   - d_keep[offsets[f] + max(nkeep[f], 0) .. offsets[f + 1]) is scratch: unspecified after the call.
+ *   - Deviation from the reference: two entries that re-key to the SAME key outside the frame make the reference's assert
+ *     (pflib.py:518) fire; the library (and the C oracle's fsq_o_consolidate) check collisions only inside the frame and keep
+ *     both.  Neither fitter can put a centre there: the LM fit bounds the window centre to [2, 3] (pflib.py:204-212), the
+ *     Monte-Carlo fit clips it to [0.01, 4.99] (pflib.py:153-154), around a pixel at least 2 from every edge - the key lies
+ *     within 2 of the pixel, inside the frame.  Only a caller's own rows reach it (tests/golden/consolidate_limits.npz, case outside_collision).
+ * Returns FSQ_EINVAL for radius < 2, H < 5, W < 5, n_fields < 1 or a null pointer, FSQ_ENOMEM for a workspace below
+ * fsq_consolidate_workspace_bytes; nothing is written then.
  */
 int fsq_consolidate(FsqRow* d_rows, const int32_t* d_counts, const int32_t* d_offsets, int n_fields, int H, int W,
                     double r2_threshold,

@@ -9,7 +9,7 @@ fluorosequencingimageanalysis_amd/synth.py.  The .npz files hold DATA only
 
 Usage (about 4 minutes on 8 cores):
   NPY_DISABLE_CPU_FEATURES="AVX512F AVX512CD AVX512_SKX AVX512_CLX AVX512_CNL AVX512_ICL AVX512_SPR" \
-      python oracle/gen_golden.py [--only fields|reg|reg_limits|detect_limits|kat|phot|phot_wide|phot_limits|track_limits|centroid_limits|degen|params|tiny|wide|textbook|io|loader|track|track_long|centroid|centroid_wide]
+      python oracle/gen_golden.py [--only fields|reg|reg_limits|detect_limits|consolidate_limits|kat|phot|phot_wide|phot_limits|track_limits|centroid_limits|degen|params|tiny|wide|textbook|io|loader|track|track_long|centroid|centroid_wide]
 
 Golden sets: G1 per-ROI fits, G2 candidate lists, G3 full
 find_peptides tables, G4 phase_correlate tuples, G5 known-answer tests.
@@ -1071,6 +1071,89 @@ def gen_detect_limits():
     print("detect_limits.npz:", len(names), "cases,", os.path.getsize(os.path.join(GOLD, "detect_limits.npz")), "bytes", flush=True)
 
 
+def gen_consolidate_limits():
+    """The R^2 filter, consolidation and re-key loops of the unmodified find_peptides (pflib.py:441-520) on every field of every
+    recorded case of tests/_consolidate_limit_cases.py -> tests/golden/consolidate_limits.npz.  The loaded module's
+    _psf_candidates and _fit_2d_gaussian are replaced, at run time, by stand-ins that hand back the field's candidate pixels and
+    its crafted (h_0, w_0, ..., fit_img); r_2 is the reference's own, from the frame's patch and that fit_img.  Recorded per field:
+    h0, w0 and r_2 of every candidate as the reference holds them (bit patterns, each from a run on that candidate alone at
+    r_2_threshold = -inf, where nothing is filtered or consolidated), and per rounding mode - the module's round as refload
+    injects it (Python 2) and Python 3's built-in - the kept candidates in the dict's order with their keys, or -1 where
+    AssertionError was raised.  Run time: 6 s."""
+    import builtins
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _consolidate_limit_cases as C
+    pf = _ref().pf
+    py2_round = pf.round
+    one = np.float64(1.0)
+    state = {}
+
+    def stand_in_candidates(image, **kwargs):
+        return list(state["pixels"])
+
+    def stand_in_fit(sub_img, implementation="agpy"):
+        f, i = state["field"], state["order"][state["k"]]
+        state["k"] += 1
+        fh = np.float64(f.fh[i])
+        if i in f.exact:                # (h_0 + h - 2.5 in long double gives the centre exactly; float64 has no such fh)
+            fh = np.longdouble(f.exact[i]) - np.longdouble(int(f.h[i])) + np.longdouble(2.5)
+        fit = f.fit_image(i, sub_img)
+        state["made"][id(fit)] = i
+        state["alive"].append(fit)
+        return fh, np.float64(f.fw[i]), one, one, one, one, one * 0, fit
+
+    def run(f, img, order, thr, radius):
+        state.update(field=f, order=list(order), k=0, pixels=[(int(f.h[i]), int(f.w[i])) for i in order], made={}, alive=[])
+        with np.errstate(all="ignore"):
+            return pf.find_peptides(img, r_2_threshold=thr, consolidation_radius=radius)
+    pf._psf_candidates, pf._fit_2d_gaussian = stand_in_candidates, stand_in_fit
+    out = dict(names=[], n_fields=[], n_cand=[], h0_bits=[], w0_bits=[], r2_bits=[])
+    for m in ("py2", "py3"):
+        out.update({"nkeep_" + m: [], "kept_" + m: [], "keys_" + m: []})
+    for c in C.cases():
+        if not c.recorded:
+            continue
+        out["names"].append(c.name)
+        out["n_fields"].append(len(c.fields))
+        n_assert = 0
+        for f in c.fields:
+            img = f.image(c.H, c.W)
+            pf.round = py2_round
+            held = []
+            for i in range(len(f)):
+                (psf,) = run(f, img, [i], -np.inf, 2).values()
+                held.append((np.float64(psf[0]), np.float64(psf[1]), np.float64(psf[10])))
+                assert np.float64(psf[0]) == psf[0]
+            held = np.array(held, np.float64).reshape(-1, 3)
+            out["n_cand"].append(len(f))
+            for k, name in enumerate(("h0_bits", "w0_bits", "r2_bits")):
+                out[name].append(held[:, k].copy().view(np.uint64))
+            for m, rnd in (("py2", py2_round), ("py3", builtins.round)):
+                pf.round = rnd
+                try:
+                    psfs = run(f, img, range(len(f)), c.thr, c.radius)
+                except AssertionError:
+                    out["nkeep_" + m].append(-1)
+                    n_assert += 1
+                    continue
+                kept = [state["made"][id(psf[8])] for psf in psfs.values()]     # (fit_img is the very array the stand-in made)
+                assert len(set(kept)) == len(kept)
+                out["nkeep_" + m].append(len(kept))
+                out["kept_" + m].append(np.array(kept, np.int16))
+                out["keys_" + m].append(np.array(list(psfs.keys()), np.int16).reshape(-1, 2))
+        pf.round = py2_round
+        print("consolidate_limits:", c.name, (c.H, c.W), "radius", c.radius, "fields", len(c.fields), "asserting (both modes)", n_assert, flush=True)
+    arrays = dict(names=np.array(out["names"]), n_fields=np.array(out["n_fields"], np.int32), n_cand=np.array(out["n_cand"], np.int32))
+    for name in ("h0_bits", "w0_bits", "r2_bits"):
+        arrays[name] = np.concatenate(out[name]).astype(np.uint64)
+    for m in ("py2", "py3"):
+        arrays["nkeep_" + m] = np.array(out["nkeep_" + m], np.int32)
+        arrays["kept_" + m] = np.concatenate(out["kept_" + m]).astype(np.int16)
+        arrays["keys_" + m] = np.concatenate(out["keys_" + m]).astype(np.int16).reshape(-1, 2)
+    np.savez_compressed(os.path.join(GOLD, "consolidate_limits.npz"), **arrays)
+    print("consolidate_limits.npz:", len(out["names"]), "cases,", os.path.getsize(os.path.join(GOLD, "consolidate_limits.npz")), "bytes", flush=True)
+
+
 def gen_io():
     """On-disk formats: the reference's own save_psfs_csv / save_psfs_pkl / _psfs_filename on its own
     find_peptides result for field f5 (pflib.py:569-711).  The CSV text is what the reference writes under THIS
@@ -1164,6 +1247,8 @@ def main():
         gen_reg_limits()
     if a.only in ("", "detect_limits"):
         gen_detect_limits()
+    if a.only in ("", "consolidate_limits"):
+        gen_consolidate_limits()
     if a.only in ("", "phot"):
         gen_photometry()
     if a.only in ("", "phot_wide"):

@@ -137,6 +137,29 @@ def find_peptides(img, med_size=5, K=DEFAULT_K, c_std=2.0, r2_thr=0.7, radius=4,
     return rows[:nc.value].copy(), fits[:nc.value].copy(), keep[:nk.value].copy(), key[:nk.value].copy()
 
 
+def consolidate(h, w, h0, w0, r2, H, W, r2_thr, radius, py2=True, libm=False):
+    """fsq_o_consolidate alone (pflib.py:466, 477-519) on one field's candidate table in raster order, 2 <= h < H - 2:
+    -> (kept candidate numbers in the reference's dict order, their keys int32[k, 2]); AssertionError where pflib.py:518 fires.
+    py2: Python 2's round (half away from zero), otherwise Python 3's (half to even)."""
+    n = len(h)
+    rows = np.zeros(max(n, 1), ROW_DTYPE)
+    rows["h"][:n], rows["w"][:n], rows["h0"][:n], rows["w0"][:n], rows["r2"][:n] = h, w, h0, w0, r2
+    if n and not ((rows["h"][:n] >= 0) & (rows["h"][:n] < H) & (rows["w"][:n] >= 0) & (rows["w"][:n] < W)).all():
+        raise ValueError("candidate pixel outside the frame")
+    keep = np.zeros(max(n, 1), np.int32)
+    key = np.zeros((max(n, 1), 2), np.int32)
+    f = lib(libm).fsq_o_consolidate
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                  ctypes.c_void_p, ctypes.c_void_p]
+    nk = f(_p(rows), n, int(H), int(W), float(r2_thr), int(radius), 1 if py2 else 0, _p(keep), _p(key))
+    if nk == -4:
+        raise AssertionError("pflib.py:518 assert")
+    if nk < 0:
+        raise ValueError("oracle consolidate error %d" % nk)
+    return keep[:nk].copy(), key[:nk].copy()
+
+
 def enorm(x, inc=1):
     x = np.ascontiguousarray(x, dtype=np.float64)
     n = (len(x) + inc - 1) // inc

@@ -7,46 +7,9 @@ larger than the one-pass register window), fields of one block's 8 and 16 waves 
 import numpy as np
 import pytest
 
+from _consolidate_limit_cases import reference_consolidate    # (the one restatement, pinned to the reference by test_consolidate_limits_host.py)
+
 pytestmark = pytest.mark.gpu
-
-
-def py2_round(x):
-    return int(np.floor(x + 0.5)) if x >= 0 else int(np.ceil(x - 0.5))
-
-
-def reference_consolidate(h, w, h0, w0, r2, H, W, thr, radius):
-    """-> (kept candidate numbers in the reference's dict order, their keys) or None when the assert of pflib.py:518 fires."""
-    bins = {}
-    for i in range(len(h)):
-        if not (r2[i] < thr):                                   # pflib.py:466 (NaN passes)
-            bins.setdefault((int(h[i]), int(w[i])), i)
-    for (hh, ww), i in list(bins.items()):                      # pflib.py:479-512
-        if (hh, ww) not in bins:
-            continue
-        dead = False
-        for hd in range(max(0, hh - radius - 2), min(hh + radius + 3, H)):
-            for wd in range(max(0, ww - radius - 2), min(ww + radius + 3, W)):
-                if (hd == hh and wd == ww) or (hd, wd) not in bins:
-                    continue
-                k = bins[(hd, wd)]
-                if (h0[i] - h0[k]) ** 2 + (w0[i] - w0[k]) ** 2 > radius ** 2:
-                    continue
-                if r2[i] > r2[k]:
-                    del bins[(hd, wd)]
-                else:
-                    del bins[(hh, ww)]
-                    dead = True
-                    break
-            if dead:
-                break
-    for (hh, ww), i in list(bins.items()):                      # pflib.py:514-519
-        hr, wr = py2_round(h0[i]), py2_round(w0[i])
-        if hr != hh or wr != ww:
-            del bins[(hh, ww)]
-            if (hr, wr) in bins:
-                return None
-            bins.setdefault((hr, wr), i)
-    return list(bins.values()), list(bins.keys())
 
 
 def make_field(rng, H, W, kind):
