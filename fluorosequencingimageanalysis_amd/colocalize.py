@@ -18,22 +18,33 @@ signal_sweep.joint_signals_of_fits' rule: a channel without a member is dark (a 
 fails the downstep filter is rejected (on_filtered='dark': that channel counts as dark; a molecule left with no lit channel is
 rejected all the same), a molecule with a lit channel whose second fit found nothing counts into none_count.
 
+The channels' integer offsets are an input, or estimated from the tracks themselves (include/fsq_channel_offset.h;
+estimate_offset_device, estimate_offset_records, estimate_offsets_records, joint_observed_records(offsets='estimate')): all pairs
+of one field vote for their displacement a - b within a window, every offset of [-max_shift, max_shift]^2 is scored by the
+pairs it brings within the match's radius, and the largest score wins, ties to the smallest (dh^2 + dw^2, dh, dw).  Every
+further channel is estimated against the first one, whose tracks the molecules start from.
+
 Limits: at most 4 letters, tables of one frame count of at most 64, |coordinate| < 2^30 after the offset (ValueError), and the
 joint key's (signal_sweep: NotImplementedError naming the drop limit, ValueError naming table_slots=)."""
+import math
+import re
+
 import numpy as np
 
+from . import _host_channel_offset as HO
 from . import _host_colocalize as H
+from . import _native_channel_offset as NCO
 from . import _native_colocalize as NCL
 from . import engine as _engine
 
 ON_FILTERED = ('reject', 'dark')
+ESTIMATE = 'estimate'
 
 
 # ---- one match ----
 
-def _launch_match(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, radius_sq):
-    """fsq_colocalize_match on device tensors: (match_of_a, match_of_b, dist_sq_of_a, bad int32 [1]).  Enqueued on the current
-    stream, not synchronised."""
+def _segment_sizes(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off):
+    """(n_a, n_b, n_seg) of the five tensors that fsq_colocalize_match and fsq_channel_offset_votes share, after their checks."""
     torch = _engine._torch()
     n_a, n_b, n_seg = int(d_a_hw.shape[0]), int(d_b_hw.shape[0]), int(d_a_off.numel()) - 1
     tensors = (d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off)
@@ -49,6 +60,14 @@ def _launch_match(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, radius_sq):
         raise ValueError("contiguous tensors on one GPU are needed")
     if max(n_a, n_b, n_seg) >= 1 << 31:
         raise ValueError("fewer than 2^31 positions and segments are needed")
+    return n_a, n_b, n_seg
+
+
+def _launch_match(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, radius_sq):
+    """fsq_colocalize_match on device tensors: (match_of_a, match_of_b, dist_sq_of_a, bad int32 [1]).  Enqueued on the current
+    stream, not synchronised."""
+    torch = _engine._torch()
+    n_a, n_b, n_seg = _segment_sizes(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off)
     radius_sq = int(radius_sq)
     if not 0 <= radius_sq < 1 << 63:
         raise ValueError("radius_sq must not be negative")
@@ -93,6 +112,120 @@ def match_records(a_hw, a_seg, a_off, b_hw, b_off, radius_sq, host=False, device
     out = match_device(up(a_hw, np.int32), up(np.asarray(a_seg).reshape(-1), np.int32), up(np.asarray(a_off).reshape(-1), np.int64),
                        up(b_hw, np.int32), up(np.asarray(b_off).reshape(-1), np.int64), radius_sq)
     return tuple(t.cpu().numpy() for t in out)
+
+
+# ---- the offset between two channels (include/fsq_channel_offset.h) ----
+
+def _launch_votes(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, W):
+    """fsq_channel_offset_votes on device tensors: (votes int64 [2W + 1, 2W + 1], bad int32 [1]).  Enqueued on the current
+    stream, not synchronised."""
+    torch = _engine._torch()
+    n_a, n_b, n_seg = _segment_sizes(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off)
+    W = int(W)
+    if not 0 <= W <= NCO.MAX_W:
+        raise ValueError("W must be 0 .. %d" % NCO.MAX_W)
+    dev = d_a_hw.device
+    d_votes = torch.empty((2 * W + 1, 2 * W + 1), dtype=torch.int64, device=dev)
+    d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None                                  # noqa: E731
+    _engine.launch(NCO.lib().fsq_channel_offset_votes, "fsq_channel_offset_votes", dev, ptr(d_a_hw), ptr(d_a_seg), d_a_off.data_ptr(),
+                   d_b_off.data_ptr(), ptr(d_b_hw), W, n_a, n_b, n_seg, d_votes.data_ptr(), d_bad.data_ptr())
+    return d_votes, d_bad
+
+
+def offset_votes_device(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, W):
+    """The votes of A against B on the device, tensors as for match_device: the CUDA tensor V int64 [2W + 1, 2W + 1],
+    V[dh + W, dw + W] = the pairs (a, b) of one field with a - b = (dh, dw), 0 <= W <= 64.  Segments or offsets that are not
+    well formed, or a field of 2^24 or more b's, raise ValueError."""
+    _check_device_positions(d_a_hw, "a_hw")
+    _check_device_positions(d_b_hw, "b_hw")
+    d_votes, d_bad = _launch_votes(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, W)
+    if int(d_bad):
+        raise ValueError(HO.NOT_WELL_FORMED)
+    return d_votes
+
+
+def offset_peak_device(d_votes, R, tol_sq, scores=False):
+    """fsq_channel_offset_peak on a CUDA tensor of votes int64 [2W + 1, 2W + 1]: the record int64 [16] as a CUDA tensor (dh,
+    dw, score, runner_up, total, at_edge, n_ties, the 3 x 3 of V around the peak); scores=True: (record, S int64 [2R + 1,
+    2R + 1]).  0 <= R, 0 <= tol_sq and R + isqrt(tol_sq) <= W are needed (ValueError).  Not synchronised."""
+    torch = _engine._torch()
+    if d_votes.dtype != torch.int64 or d_votes.dim() != 2 or d_votes.shape[0] != d_votes.shape[1] or not d_votes.shape[0] & 1 \
+            or d_votes.shape[0] > 2 * NCO.MAX_W + 1 or not d_votes.is_cuda or not d_votes.is_contiguous():
+        raise ValueError("votes are a contiguous int64 CUDA tensor [2W + 1, 2W + 1] with W <= %d" % NCO.MAX_W)
+    W, R, tol_sq = int(d_votes.shape[0]) // 2, int(R), int(tol_sq)
+    if R < 0 or tol_sq < 0 or R + math.isqrt(tol_sq) > W:
+        raise ValueError("0 <= R, 0 <= tol_sq and R + isqrt(tol_sq) <= W = %d are needed" % W)
+    dev = d_votes.device
+    d_record = torch.empty(NCO.RECORD, dtype=torch.int64, device=dev)
+    d_scores = torch.empty((2 * R + 1, 2 * R + 1), dtype=torch.int64, device=dev) if scores else None
+    _engine.launch(NCO.lib().fsq_channel_offset_peak, "fsq_channel_offset_peak", dev, d_votes.data_ptr(), W, R, tol_sq,
+                   d_record.data_ptr(), d_scores.data_ptr() if scores else None)
+    return (d_record, d_scores) if scores else d_record
+
+
+def estimate_offset_device(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, max_shift=16, tol_sq=4):
+    """The integer offset to add to B's positions so that they land on A's, tensors as for match_device: the offset of
+    [-max_shift, max_shift]^2 under which the most pairs of one field lie within tol_sq of each other (ties to the smallest
+    (dh^2 + dw^2, dh, dw)).  Returns a dict: offset (dh, dw), score, runner_up (the best score further than 2 isqrt(tol_sq)
+    from the peak, -1 without such an offset), total (all votes), at_edge (the peak stands on the window's edge: the true
+    offset may lie outside), n_ties, centroid (float64 (h, w), from the 3 x 3 of votes around the peak; informational) and
+    votes (the CUDA tensor int64 [2W + 1, 2W + 1], W = max_shift + isqrt(tol_sq) <= 64, else ValueError).  Two launches; the
+    128-byte record and the error flags cross to the host."""
+    W, R, _ = HO.window(max_shift, tol_sq)
+    d_votes = offset_votes_device(d_a_hw, d_a_seg, d_a_off, d_b_hw, d_b_off, W)
+    return HO.estimate_of(offset_peak_device(d_votes, R, tol_sq).cpu().numpy(), d_votes)
+
+
+def estimate_offset_records(a_hw, a_field, b_hw, b_field, max_shift=16, radius=2, host=False, device=None):
+    """estimate_offset_device for NumPy positions [n, 2] and one field per position, the tolerance being the match's own
+    radius_sq_of(radius); `votes` comes back as a NumPy array.  host=True: the NumPy twin, without a GPU."""
+    tol_sq = H.radius_sq_of(radius)
+    W, R, _ = HO.window(max_shift, tol_sq)
+    a_hw, b_hw = H.check_positions(a_hw, "a_hw"), H.check_positions(b_hw, "b_hw")
+    a_field, b_field = (np.asarray(f).reshape(-1) for f in (a_field, b_field))
+    if len(a_field) != len(a_hw) or len(b_field) != len(b_hw) or any(f.size and f.dtype.kind not in "iu" for f in (a_field, b_field)):
+        raise ValueError("one integer field per position is needed")
+    ids = np.unique(np.concatenate([a_field.astype(np.int64), b_field.astype(np.int64)]))
+    a_order, a_seg, a_off = H.grouped(a_field, ids)
+    b_order, _, b_off = H.grouped(b_field, ids)
+    if host:
+        V = HO.votes(a_hw[a_order], a_seg, a_off, b_hw[b_order], b_off, W)
+        return HO.estimate_of(HO.peak(V, R, tol_sq), V)
+    torch = _engine._torch()
+    dev = torch.device(device or "cuda")
+    up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dt)).to(dev)           # noqa: E731
+    out = estimate_offset_device(up(a_hw[a_order], np.int32), up(a_seg, np.int32), up(a_off, np.int64), up(b_hw[b_order], np.int32),
+                                 up(b_off, np.int64), max_shift, tol_sq)
+    out["votes"] = out["votes"].cpu().numpy()
+    return out
+
+
+def estimate_offsets_records(tables_hw_field, radius, max_shift=16, offsets=None, min_score=1, host=False, device=None):
+    """The offsets of K channels for molecules_*: tables_hw_field per channel (hw [n, 2], field [n]); offsets: None, or per
+    channel (dh, dw) or None for a channel to estimate (channel 0: None is (0, 0)).  Every channel k >= 1 without an offset is
+    estimated against channel 0 - a molecule keeps its first member's position, so channel 0 is the anchor - after channel 0's
+    own offset was applied: K - 1 vote launches at the most.  Returns (offsets [K] of (dh, dw), estimates [K]:
+    estimate_offset_records' dict of an estimated channel, None for the others).  A score below min_score raises ValueError
+    naming the channel and max_shift=."""
+    tables = list(tables_hw_field)
+    K = len(tables)
+    offsets = [None] * K if offsets is None else list(offsets)
+    if len(offsets) != K:
+        raise ValueError("one (dh, dw) offset, or None, per channel is needed")
+    given = [(0, 0) if o is None else o for o in offsets]
+    checked = H.checked_tables(tables, given)                          # (the given offsets are applied here, exactly)
+    out, estimates = list(given), [None] * K
+    for k in range(1, K):
+        if offsets[k] is not None:
+            continue
+        est = estimate_offset_records(checked[0][0], checked[0][1], checked[k][0], checked[k][1], max_shift, radius, host=host,
+                                      device=device)
+        if est["score"] < int(min_score):
+            raise ValueError("channel %d: the best offset within max_shift=%d pairs %d tracks, fewer than min_score=%d"
+                             % (k, int(max_shift), est["score"], int(min_score)))
+        out[k], estimates[k] = est["offset"], est
+    return out, estimates
 
 
 # ---- the merge over K channels ----
@@ -198,12 +331,31 @@ def _letter_offsets(offsets, letters):
     return [tuple(offsets.get(L, (0, 0))) for L in letters]
 
 
+def _offsets_to_estimate(offsets, letters):
+    """(offsets per letter with None where one is to be estimated, whether any is): offsets='estimate' asks for every letter
+    but the first, a dict may ask with the value 'estimate' letter by letter."""
+    if isinstance(offsets, str):
+        if offsets != ESTIMATE:
+            raise ValueError("offsets must be a dict {letter: (dh, dw)}, None or 'estimate'")
+        return [(0, 0)] + [None] * (len(letters) - 1), True
+    asked = {L for L, o in (offsets or {}).items() if isinstance(o, str)}
+    if not asked:
+        return _letter_offsets(offsets, letters), False
+    if any(offsets[L] != ESTIMATE for L in asked) or letters[0] in asked:
+        raise ValueError("an offset is (dh, dw) or, for a letter other than the first, 'estimate'")
+    per = _letter_offsets({L: ((0, 0) if L in asked else o) for L, o in offsets.items()}, letters)
+    return [None if L in asked else o for L, o in zip(letters, per)], True
+
+
 def joint_observed_records(tables, beta_sigma, radius=2, offsets=None, max_possible=5, ddif=0.30, allow_multidrop=True, truncate=0,
                            beta=None, no_adjustment=False, solver='enumerate', on_filtered='reject', table_slots=1024, device=None,
-                           host=False):
+                           host=False, max_shift=16, min_score=1):
     """The joint observed signals of {letter: track table}, a table being lognormal.track_table_from_photometries' or
     track_table_from_records' 5-tuple with downstep_filtered=False: (intensity [n, F], category words [n], field [n], hw [n, 2],
-    row [n]).  offsets: {letter: (dh, dw)} integers, (0, 0) where absent.  beta_sigma, ddif, truncate and beta are one value
+    row [n]).  offsets: {letter: (dh, dw)} integers, (0, 0) where absent; or 'estimate': every letter but the first is estimated
+    against the first (estimate_offsets_records: the window is max_shift, the tolerance the call's radius, a score below min_score
+    raises ValueError), or a dict with the value 'estimate' for the letters to estimate.  Only then does the returned dict gain
+    offsets {letter: (dh, dw)} and offset_estimates {estimated letter: estimate_offset_records' dict}.  beta_sigma, ddif, truncate and beta are one value
     for all letters or a dict {letter: value}.  Returns a dict:
 
       signals       {joint_signal: n}, what sweep_peptide --observed and signal_sweep.score_records take
@@ -248,7 +400,13 @@ def joint_observed_records(tables, beta_sigma, radius=2, offsets=None, max_possi
     HC.check_frames(F, allow_multidrop)
     sigmas, ddifs, truncs, betas = (_per_letter(v, name, letters) for v, name in
                                     ((beta_sigma, 'beta_sigma'), (ddif, 'ddif'), (truncate, 'truncate'), (beta, 'beta')))
-    hw_field, offs = [(t[3], t[2]) for t in tabs], _letter_offsets(offsets, letters)
+    hw_field, (offs, estimated) = [(t[3], t[2]) for t in tabs], _offsets_to_estimate(offsets, letters)
+    if estimated:
+        try:
+            offs, estimates = estimate_offsets_records(hw_field, radius, max_shift, offs, min_score, host=host, device=device)
+        except ValueError as e:                                        # (a channel by its letter)
+            k = re.match(r"channel (\d+): ", str(e))
+            raise ValueError("letter %s: %s" % (letters[int(k.group(1))], str(e)[k.end():])) if k else e
     if host:
         mols = H.molecules(hw_field, radius, offs)
     else:
@@ -298,6 +456,10 @@ def joint_observed_records(tables, beta_sigma, radius=2, offsets=None, max_possi
                                        device=device)
     to_np = (lambda a: a) if host else (lambda a: a.cpu().numpy())
     M, n_rejected = int(member.shape[1]), int(rejected.sum())
-    return {"signals": signals, "n_molecules": M, "n_rejected": n_rejected, "total_count": M - n_rejected, "none_count": none_count,
-            "labels": letters, "molecules": mols, "rejected": to_np(rejected), "kept": kept,
-            "fit_index": to_np(xp.where(lit, index, xp.full_like(index, -1))), "channels": channels}
+    out = {"signals": signals, "n_molecules": M, "n_rejected": n_rejected, "total_count": M - n_rejected, "none_count": none_count,
+           "labels": letters, "molecules": mols, "rejected": to_np(rejected), "kept": kept,
+           "fit_index": to_np(xp.where(lit, index, xp.full_like(index, -1))), "channels": channels}
+    if estimated:
+        out["offsets"] = dict(zip(letters, offs))
+        out["offset_estimates"] = {L: e for L, e in zip(letters, estimates) if e is not None}
+    return out

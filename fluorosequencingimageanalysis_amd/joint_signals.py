@@ -3,12 +3,17 @@ channels are colocalised on the GPU, every channel is fitted with the lognormal 
 tallied (colocalize.joint_observed_records) - the file that sweep_peptide SEQUENCE KC --observed reads.
 
   python -m fluorosequencingimageanalysis_amd.joint_signals TRACKS.csv --labels K=ch1 C=ch2 [--radius 2 --offset C=1,-2
-         --beta_sigma K=..,C=.. --ddif .. --beta .. --truncate N --max_possible 5 --no_adjustment --no_multidrop
+         --estimate_offset --max_shift 16 --min_score 1 --beta_sigma K=..,C=.. --ddif .. --beta .. --truncate N --max_possible 5 --no_adjustment --no_multidrop
          --solver {enumerate,dp} --on_filtered {reject,dark} --table_slots N --host --device D --output_directory DIR]
 
 TRACKS.csv is the table basic_experiment_script or remainder_correction wrote; --labels names the channel of every label
 letter.  Two tracks of one field are the same molecule when each is the other's nearest within --radius pixels, after the
-channel's integer --offset LETTER=DH,DW was added to its positions (estimating that offset is the caller's).  --beta_sigma,
+channel's integer --offset LETTER=DH,DW was added to its positions.  --estimate_offset estimates the offsets that --offset
+does not name, for every letter but the first (in sorted order) against the first: the shift of at most --max_shift pixels
+either way under which the most tracks of the two channels lie within --radius of each other (colocalize.
+estimate_offsets_records; fewer than --min_score such pairs is an error).  It prints one line per estimated letter - offset,
+score, runner-up, centroid, and a warning when the offset stands on the window's edge - and writes ChannelOffsets_<hash>.csv
+(LETTER, DH, DW, SCORE, RUNNER_UP, TOTAL, AT_EDGE, CENTROID_H, CENTROID_W).  --beta_sigma,
 --ddif and --beta take one number or K=..,C=...  --on_filtered: a molecule with a track that fails the downstep filter is left
 out (reject, the default), or that channel counts as dark.  Prints the counts and every channel's alpha and beta, and writes
 
@@ -59,6 +64,10 @@ def build_parser():
     p.add_argument('--labels', nargs='+', type=label_channel, required=True, help="LETTER=CHANNEL for every label letter, e.g. K=ch1 C=ch2.")
     p.add_argument('--radius', type=float, default=2.0, help="Tracks at most this far apart can be one molecule.")
     p.add_argument('--offset', nargs='+', type=letter_offset, default=[], help="LETTER=DH,DW: integers added to the channel's positions.")
+    p.add_argument('--estimate_offset', action='store_true', default=False,
+                   help="Estimate the offsets --offset does not name, for every letter but the first, from the tracks themselves.")
+    p.add_argument('--max_shift', type=int, default=16, help="With --estimate_offset: the largest shift looked for, in pixels either way.")
+    p.add_argument('--min_score', type=int, default=1, help="With --estimate_offset: fewer pairs than this under the best offset is an error.")
     p.add_argument('--beta_sigma', type=per_letter, default=0.20, help="Lognormal shape parameter: a number, or K=..,C=..")
     p.add_argument('--ddif', type=per_letter, default=0.30, help="Dye-dye interaction factor: a number, or K=..,C=..")
     p.add_argument('--beta', type=per_letter, default=None, help="Manually specify 1-fluor intensity: a number, or K=..,C=..")
@@ -114,6 +123,16 @@ def write_molecules_csv(path, out, tables):
             w.writerow([field, h, wd, rejected] + [x for col in cells for x in col[m]])
 
 
+def write_offsets_csv(path, estimates):
+    """ChannelOffsets_<hash>.csv of joint_observed_records' offset_estimates: one line per estimated letter."""
+    with open(path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(['LETTER', 'DH', 'DW', 'SCORE', 'RUNNER_UP', 'TOTAL', 'AT_EDGE', 'CENTROID_H', 'CENTROID_W'])
+        for L, e in estimates.items():
+            w.writerow([L, e["offset"][0], e["offset"][1], e["score"], e["runner_up"], e["total"], int(e["at_edge"]),
+                        repr(e["centroid"][0]), repr(e["centroid"][1])])
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -124,10 +143,15 @@ def main(argv=None):
     if len(offsets) != len(args.offset) or set(offsets) - set(channel_of):
         parser.error("--offset: every letter once, and only letters of --labels")
     tables = read_tables(os.path.abspath(args.tracks[0]), channel_of)
+    extra = {}
+    if args.estimate_offset:
+        to_estimate = [L for L in sorted(channel_of)[1:] if L not in offsets]
+        offsets.update({L: colocalize.ESTIMATE for L in to_estimate})
+        extra = dict(max_shift=args.max_shift, min_score=args.min_score)
     out = colocalize.joint_observed_records(
         tables, args.beta_sigma, radius=args.radius, offsets=offsets, max_possible=args.max_possible, ddif=args.ddif,
         allow_multidrop=not args.no_multidrop, truncate=args.truncate, beta=args.beta, no_adjustment=args.no_adjustment,
-        solver=args.solver, on_filtered=args.on_filtered, table_slots=args.table_slots, device=args.device, host=args.host)
+        solver=args.solver, on_filtered=args.on_filtered, table_slots=args.table_slots, device=args.device, host=args.host, **extra)
     output_directory = os.path.abspath(args.output_directory[0])
     if not os.path.exists(output_directory):
         os.makedirs(output_directory)
@@ -137,6 +161,18 @@ def main(argv=None):
     with open(signals_path, 'wb') as f:
         pickle.dump(out["signals"], f, protocol=2)
     write_molecules_csv(molecules_path, out, tables)
+    paths = (signals_path, molecules_path)
+    if args.estimate_offset:
+        estimates = out.get("offset_estimates", {})
+        for L, e in estimates.items():
+            print("Letter " + L + " (" + channel_of[L] + "): offset " + str(e["offset"][0]) + "," + str(e["offset"][1]) + " against letter " +
+                  out["labels"][0] + ", score " + str(e["score"]) + " of " + str(e["total"]) + " votes, runner-up " + str(e["runner_up"]) +
+                  ", centroid " + repr(e["centroid"][0]) + "," + repr(e["centroid"][1]) +
+                  ("; WARNING: the offset stands on the edge of --max_shift " + str(args.max_shift) + ", the true one may lie outside"
+                   if e["at_edge"] else ""))
+        offsets_path = os.path.join(output_directory, "ChannelOffsets_" + timestamp_hash + ".csv")
+        write_offsets_csv(offsets_path, estimates)
+        paths += (offsets_path,)
     for L in out["labels"]:
         chain = out["channels"][L]
         print("Letter " + L + " (" + channel_of[L] + "): " + str(len(tables[L][0])) + " tracks, " + str(chain["total_count"]) +
@@ -147,7 +183,9 @@ def main(argv=None):
     print("Distinct joint signals: " + str(len(out["signals"])))
     print("Saved joint signals to " + signals_path)
     print("Saved molecules to " + molecules_path)
-    return signals_path, molecules_path
+    if args.estimate_offset:
+        print("Saved channel offsets to " + paths[2])
+    return paths
 
 
 if __name__ == "__main__":
