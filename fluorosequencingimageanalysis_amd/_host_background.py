@@ -1,5 +1,7 @@
 """The iterative background correction with numpy on the host: what fsq_background_iterate (include/fsq_background.h)
-computes, the `device=None` route of background.py.  A problem is the dict of arrays background.pack_problem gives."""
+computes, the `device=None` route of background.py.  A problem is the dict of arrays background.pack_problem gives; one of
+background.joint_pack_problem carries "n_channels" and its codes are joint keys, whose neighbours joint_neighbour_lists
+gives (the definition of include/fsq_background_joint.h and DESIGN.md 4.32; it runs on the host only)."""
 import itertools
 import math
 
@@ -44,6 +46,58 @@ def neighbour_lists(code, num_cycles, include_multidrop, rows=None, chunk=2048):
             at = np.searchsorted(sorted_code, c)
             at_c = np.minimum(at, max(len(code) - 1, 0))
             found = (at < len(code)) & (sorted_code[at_c] == c) if len(code) else np.zeros(c.shape, bool)
+            idx = np.where(found, order[at_c], -1)
+            for r, row in enumerate(part):
+                out[row] = idx[r][ok[r]].astype(np.int64)
+    return out
+
+
+def joint_decode(code, n_channels):
+    """(cycles int64 [n, JOINT_MAX_DROPS] with 0 beyond the drops, drops int64 [n]) of uint64 joint keys of n_channels letters:
+    a key's drops are its non-zero drop fields, read from the first on."""
+    from ._host_signal_sweep import JOINT_DROP_BITS, JOINT_MAX_DROPS
+    code = np.asarray(code, dtype=np.uint64).reshape(-1)
+    B, cap = JOINT_DROP_BITS[n_channels], min(NB.JOINT_MAX_DROPS, JOINT_MAX_DROPS[n_channels])
+    fields = np.stack([(code >> np.uint64(4 + B * i)) & np.uint64((1 << B) - 1) for i in range(cap)], axis=1).astype(np.int64)
+    drops = np.cumprod(fields != 0, axis=1).sum(axis=1)
+    cycles = np.zeros((len(code), NB.JOINT_MAX_DROPS), np.int64)
+    cycles[:, :cap] = np.where(np.arange(cap)[None, :] < drops[:, None], fields & 63, 0)
+    return cycles, drops
+
+
+def joint_neighbour_lists(code, n_channels, num_cycles, include_multidrop, rows=None, chunk=256):
+    """neighbour_lists for joint keys of n_channels letters (include/fsq_background_joint.h): the cycles perturbed in
+    itertools.product order, letters and starts kept, those out of 0 < cycle <= num_cycles or (multidrop excluded) with a repeated cycle left out, each looked up as it stands: a tuple that no longer ascends by
+    (cycle, letter) is no key's code and gives -1."""
+    from ._host_signal_sweep import JOINT_DROP_BITS
+    code = np.asarray(code, dtype=np.uint64)
+    rows = np.arange(len(code)) if rows is None else np.asarray(rows, dtype=np.int64)
+    B = JOINT_DROP_BITS[n_channels]
+    num_cycles = min(int(num_cycles), NB.JOINT_MAX_CYCLES)
+    order = np.argsort(code, kind='stable')
+    sorted_code = code[order]
+    cyc, drops = joint_decode(code[rows], n_channels)
+    out = [np.zeros(0, np.int64)] * len(rows)
+    for d in np.unique(drops):
+        d = int(d)
+        if d < 1:
+            continue
+        E = np.array([e for e in itertools.product((-1, 0, 1), repeat=d) if any(e)], dtype=np.int64).reshape(-1, d)
+        sel = np.flatnonzero(drops == d)
+        shifts = np.array([4 + B * i for i in range(d)], dtype=np.uint64)
+        clear = ~np.uint64(sum(63 << (4 + B * i) for i in range(d)))
+        for a in range(0, len(sel), max(1, chunk * 728 // len(E))):
+            part = sel[a:a + max(1, chunk * 728 // len(E))]
+            cand = cyc[part, None, :d] + E[None, :, :]                              # [n, M, d]
+            ok = ((cand > 0) & (cand <= num_cycles)).all(axis=2)
+            if not include_multidrop and d > 1:
+                s = np.sort(cand, axis=2)
+                ok &= (s[:, :, 1:] != s[:, :, :-1]).all(axis=2)
+            rest = code[rows[part]] & clear
+            c = rest[:, None] | ((cand & 63).astype(np.uint64) << shifts[None, None, :]).sum(axis=2, dtype=np.uint64)
+            at = np.searchsorted(sorted_code, c)
+            at_c = np.minimum(at, max(len(code) - 1, 0))
+            found = (at < len(code)) & (sorted_code[at_c] == c)
             idx = np.where(found, order[at_c], -1)
             for r, row in enumerate(part):
                 out[row] = idx[r][ok[r]].astype(np.int64)
@@ -98,7 +152,10 @@ def iterate(prob, max_iterations, accepted_cap, undefined_cap, elements=1 << 22)
     ap, sp = np.asarray(prob["def_avg"], dtype=np.float64), np.asarray(prob["def_std"], dtype=np.float64)
     thr = float(prob["sigma_threshold"])
     N, D = len(count), len(def_key)
-    nbs = neighbour_lists(prob["code"], int(prob["num_cycles"]), bool(prob["include_multidrop"]))
+    if prob.get("n_channels") is None:
+        nbs = neighbour_lists(prob["code"], int(prob["num_cycles"]), bool(prob["include_multidrop"]))
+    else:
+        nbs = joint_neighbour_lists(prob["code"], int(prob["n_channels"]), int(prob["num_cycles"]), bool(prob["include_multidrop"]))
     fidx = np.flatnonzero(filt)
     fpos = np.full(N, -1, np.int64)
     fpos[fidx] = np.arange(len(fidx))

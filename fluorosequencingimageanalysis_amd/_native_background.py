@@ -1,4 +1,5 @@
-"""ctypes binding of the iterative background correction of signal counts (C ABI declared in include/fsq_background.h), on the
+"""ctypes binding of the iterative background correction of signal counts (C ABI declared in include/fsq_background.h and,
+for joint signals of several colour channels, include/fsq_background_joint.h), on the
 same libfsq_hip.so handle as _native.  A sibling of _native_remainder."""
 import ctypes
 
@@ -19,6 +20,12 @@ CAPS = {"FSQ_BACKGROUND_MAX_DROPS": MAX_DROPS, "FSQ_BACKGROUND_MAX_POSITION": MA
         "FSQ_BACKGROUND_MAX_ITERATIONS": MAX_ITERATIONS, "FSQ_BACKGROUND_ZERO_TOTAL": ZERO_TOTAL,
         "FSQ_BACKGROUND_OVERFLOW_ACCEPTED": OVERFLOW_ACCEPTED, "FSQ_BACKGROUND_OVERFLOW_UNDEFINED": OVERFLOW_UNDEFINED}
 
+JOINT_MAX_DROPS = 8             # FSQ_BACKGROUND_JOINT_MAX_DROPS (include/fsq_background_joint.h)
+JOINT_MAX_NEIGHBOURS = 6560     # FSQ_BACKGROUND_JOINT_MAX_NEIGHBOURS
+JOINT_MAX_CYCLES = 63           # FSQ_BACKGROUND_JOINT_MAX_CYCLES
+JOINT_CAPS = {"FSQ_BACKGROUND_JOINT_MAX_DROPS": JOINT_MAX_DROPS, "FSQ_BACKGROUND_JOINT_MAX_NEIGHBOURS": JOINT_MAX_NEIGHBOURS,
+              "FSQ_BACKGROUND_JOINT_MAX_CYCLES": JOINT_MAX_CYCLES}
+
 _P = ctypes.c_void_p
 POINTER_FIELDS = ("key_off", "def_off", "first_off", "rest_off", "num_cycles", "include_multidrop", "sigma_threshold", "code",
                   "sorted_code", "sorted_index", "filter", "nb_off", "def_key", "def_avg", "def_std", "und_first", "und_rest",
@@ -38,5 +45,9 @@ _SIGS = {
     "fsq_background_iterate": (ctypes.c_int, [ctypes.POINTER(FsqBackgroundArgs), _P, ctypes.c_int64, _P]),
 }
 EXPORTED = tuple(_SIGS)
+_JOINT_SIGS = {                     # include/fsq_background_joint.h
+    "fsq_background_neighbour_means": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
+}
+JOINT_EXPORTED = tuple(_JOINT_SIGS)
 
-lib = N.bind(_SIGS)                 # the library handle of _native.lib() with the background entries bound
+lib = N.bind(dict(_SIGS, **_JOINT_SIGS))    # the library handle of _native.lib() with the background entries bound

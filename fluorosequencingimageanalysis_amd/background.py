@@ -22,12 +22,21 @@ lacks whose z-score at a percent of 0 is above the threshold (ValueError, the sa
 NaN to integer`); more than MAX_DROPS drops per key, positions outside 0 .. MAX_POSITION, more than MAX_GROUPS starting
 intensities (NotImplementedError); counts that are not finite or whose magnitudes add up to more than 2^53, beyond which the
 reference's integer total is no float sum (ValueError).  `max_iterations` passes without a stop raise RuntimeError; the
-reference has no such cap.  `background_device` takes device tensors as they are and checks their shapes and types only."""
+reference has no such cap.  `background_device` takes device tensors as they are and checks their shapes and types only.
+
+Two-colour experiments: joint signals (decrements, zeros, starts) of several label letters, by this package's definition
+(the reference stops at one letter).  A key is a remainder when not all(zeros), multidrop when a cycle repeats
+whatever the letters, and its neighbours are its own tuple with the cycles perturbed, looked up as they stand.
+`joint_pack_problem` and `joint_background_records` run the iteration on joint keys with numpy on the host (a device raises
+NotImplementedError); `neighbour_means_records` is the interpolation of many targets in one launch of
+fsq_background_neighbour_means (include/fsq_background_joint.h).  The reference-named functions accept joint keys; their
+one-letter results do not change."""
 import ctypes
 
 import numpy as np
 
 from . import _host_background as HB
+from . import _host_signal_sweep as HS
 from . import _native_background as NB
 from . import engine as _engine
 from .pflib import _py2_round
@@ -70,6 +79,67 @@ def _checked_key(key):
 def pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold=3, include_multidrop=False):
     """One problem of background_records from the dicts of iterative_peak_finding_v3, after the checks the module docstring
     names.  Returns a dict of arrays (include/fsq_background.h names them) plus "keys", the key universe in order."""
+    return _pack(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop, None)
+
+
+def _joint_limits(n_channels):
+    return min(NB.JOINT_MAX_DROPS, HS.JOINT_MAX_DROPS[n_channels])
+
+
+def _joint_letters(all_keys, labels):
+    """The sorted label letters of a joint problem, after the checks on its keys that need no code."""
+    all_keys = list(all_keys)
+    if not all(HS.is_joint(k) for k in all_keys):
+        raise ValueError("joint and one-letter keys are mixed")
+    widths = set(len(k[1]) for k in all_keys) | set(len(k[2]) for k in all_keys)
+    found = sorted(set(aa for k in all_keys for aa, c in k[0]))
+    if labels is None:
+        if len(widths) != 1 or len(found) != next(iter(widths)):
+            raise ValueError("the keys differ in their label letters, or a letter never drops: name the letters with `labels`")
+        labels = found
+    letters = tuple(sorted(set(labels)))
+    if not 1 <= len(letters) <= HS.MAX_CHANNELS:
+        raise ValueError("a joint signal has 1 .. %d label letters" % HS.MAX_CHANNELS)
+    if widths != {len(letters)} or not set(found) <= set(letters):
+        raise ValueError("the keys differ in their label letters: %r are expected" % (letters,))
+    return letters
+
+
+def _checked_joint_key(key, letters):
+    """The joint key (the 64-bit code) of a signal after the checks of _checked_key, each limit under its name."""
+    s, zeros, starts = key
+    if len(s) == 0:
+        raise ValueError("Not defined for empty signal.")
+    if not all(zeros):
+        raise ValueError("Not defined for remainders.")
+    if len(s) > _joint_limits(len(letters)):
+        raise NotImplementedError("joint keys of %d letters are limited to %d drops (FSQ_BACKGROUND_JOINT_MAX_DROPS, "
+                                  "FSQ_SIGNAL_JOINT_MAX_DROPS)" % (len(letters), _joint_limits(len(letters))))
+    if any(int(st) != st or not 0 <= st <= 15 for st in starts):
+        raise NotImplementedError("starting counts are limited to 0 .. 15 (the joint key's nibble)")
+    if any(int(c) != c or not 1 <= c <= NB.JOINT_MAX_CYCLES for aa, c in s):
+        raise NotImplementedError("cycles are limited to 1 .. %d (FSQ_BACKGROUND_JOINT_MAX_CYCLES)" % NB.JOINT_MAX_CYCLES)
+    code = HS.joint_key_of_signal(letters, key)
+    if code is None:
+        raise ValueError("%r is no joint signal of the letters %r" % (key, letters))
+    return code
+
+
+def joint_pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold=3, include_multidrop=False, labels=None):
+    """pack_problem for joint signals (decrements, zeros, starts) of several label letters: one problem of
+    joint_background_records, its codes the joint keys of _host_signal_sweep.joint_key_of_signal under the sorted letters
+    `labels` (by default the letters that drop), and "n_channels" their number.  All checks of pack_problem are carried over;
+    the limits (1 <= num_cycles <= 63, at most min(8, FSQ_SIGNAL_JOINT_MAX_DROPS(K)) drops, starts of at most 15) raise
+    NotImplementedError, mixed joint and one-letter keys or differing letter sets ValueError."""
+    num_cycles = int(num_cycles)
+    if not 1 <= num_cycles <= NB.JOINT_MAX_CYCLES:
+        raise NotImplementedError("num_cycles is limited to 1 .. %d (FSQ_BACKGROUND_JOINT_MAX_CYCLES)" % NB.JOINT_MAX_CYCLES)
+    letters = _joint_letters(list(boc_raw.keys()) + list(boc_percent.keys()) + list(ac_average.keys()) + list(ac_std.keys()), labels)
+    return _pack(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop, letters)
+
+
+def _pack(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop, letters):
+    """pack_problem (letters None) and joint_pack_problem (the sorted letters)."""
     if set(boc_raw.keys()) != set(boc_percent.keys()):
         raise ValueError("boc_raw and boc_percent don't have matching keys.")
     if set(ac_average.keys()) != set(ac_std.keys()):
@@ -88,15 +158,20 @@ def pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_thr
         if k not in index:
             index[k] = len(keys)
             keys.append(k)
-    letters, groups, code = set(), {}, np.zeros(len(keys), np.uint64)
+    seen, groups, code = set(), {}, np.zeros(len(keys), np.uint64)
     positions = []
     for k in list(keys) + [k for k in ac_average.keys() if k not in index]:
+        if letters is not None:
+            _checked_joint_key(k, letters)
+            continue
         s, si = _checked_key(k)
-        letters.update(aa for aa, pos in s)
-    if len(letters) > 1:
+        seen.update(aa for aa, pos in s)
+    if len(seen) > 1:
         raise ValueError("Currently only implemented for one label.")
 
     def code_of(k):
+        if letters is not None:
+            return _checked_joint_key(k, letters)
         s, si = k[0], k[2]
         g = groups.setdefault(si, len(groups))
         if g >= MAX_GROUPS:
@@ -126,13 +201,16 @@ def pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_thr
     if len(filt) and filt.any() and not (count < 0).any() and _seq_sum(count[filt.astype(bool)]) == 0:
         raise ZeroDivisionError("float division by zero")
     targets = np.array(sorted(set(und_first)), dtype=np.int64)
-    for row, nb in zip(targets, HB.neighbour_lists(code, num_cycles, include_multidrop, rows=targets)):
+    lists = (HB.neighbour_lists(code, num_cycles, include_multidrop, rows=targets) if letters is None else
+             HB.joint_neighbour_lists(code, len(letters), num_cycles, include_multidrop, rows=targets))
+    for row, nb in zip(targets, lists):
         if len(nb) == 0:
             raise ValueError("cannot convert float NaN to integer: %r has no neighbour within %d cycles to interpolate from"
                              % (keys[row], num_cycles))
     return {"keys": keys, "code": code, "filter": filt, "count": count, "percent": percent, "def_key": def_key, "def_avg": def_avg,
             "def_std": def_std, "und_first": np.array(und_first, dtype=np.int32), "und_rest": np.array(und_rest, dtype=np.int32),
-            "num_cycles": num_cycles, "include_multidrop": int(include_multidrop), "sigma_threshold": float(sigma_threshold)}
+            "num_cycles": num_cycles, "include_multidrop": int(include_multidrop), "sigma_threshold": float(sigma_threshold),
+            **({} if letters is None else {"n_channels": len(letters), "letters": letters})}
 
 
 # ---- the device route ----
@@ -225,6 +303,40 @@ def background_records(problems, max_iterations=DEFAULT_MAX_ITERATIONS, accepted
     index accepted by each accepting pass, up to accepted_cap) and undefined_bp (bp of every undefined key, pass after pass, up
     to undefined_cap)."""
     problems = list(problems)
+    if any(p.get("n_channels") is not None for p in problems):
+        raise ValueError("joint problems go through joint_background_records")
+    return _records(problems, max_iterations, accepted_cap, undefined_cap, device)
+
+
+def joint_background_records(problems, max_iterations=DEFAULT_MAX_ITERATIONS, accepted_cap=1024, undefined_cap=0, device=None):
+    """background_records for joint problems (the dicts of joint_pack_problem, or arrays of their names with "n_channels"), all
+    of the same number of letters, with numpy on the host (_host_background.iterate with joint_neighbour_lists).  There is no
+    device kernel for the iteration on joint keys: any device but None raises NotImplementedError; it is not quietly run on
+    the host.  The limits (num_cycles, drops, sum(3^d - 1) < 2^31) are checked before anything runs."""
+    problems = list(problems)
+    channels = set(int(p["n_channels"]) if p.get("n_channels") is not None else None for p in problems)
+    if len(channels) > 1 or None in channels:
+        raise ValueError("joint problems of one number of label letters are needed, not %r" % sorted(channels, key=repr))
+    n_channels = channels.pop() if channels else 1
+    if not 1 <= n_channels <= HS.MAX_CHANNELS:
+        raise ValueError("a joint signal has 1 .. %d label letters" % HS.MAX_CHANNELS)
+    for p in problems:
+        if not 1 <= int(p["num_cycles"]) <= NB.JOINT_MAX_CYCLES:
+            raise NotImplementedError("num_cycles is limited to 1 .. %d (FSQ_BACKGROUND_JOINT_MAX_CYCLES)" % NB.JOINT_MAX_CYCLES)
+        code = np.asarray(p["code"], dtype=np.uint64)
+        B, cap = HS.JOINT_DROP_BITS[n_channels], _joint_limits(n_channels)
+        if cap < HS.JOINT_MAX_DROPS[n_channels] and len(code) and ((code >> np.uint64(4 + B * cap)) & np.uint64((1 << B) - 1)).any():
+            raise NotImplementedError("joint keys of %d letters are limited to %d drops (FSQ_BACKGROUND_JOINT_MAX_DROPS)"
+                                      % (n_channels, cap))
+    total = sum(int((3 ** HB.joint_decode(p["code"], n_channels)[1] - 1).sum()) for p in problems)
+    if total >= 1 << 31:
+        raise ValueError("the neighbour table of one call is limited to sum(3^d - 1) < 2^31 entries; %d are asked for" % total)
+    if device is not None:
+        raise NotImplementedError("the iteration on joint signals runs on the host only: pass device=None (command line: --host)")
+    return _records(problems, max_iterations, accepted_cap, undefined_cap, None)
+
+
+def _records(problems, max_iterations, accepted_cap, undefined_cap, device):
     max_iterations, accepted_cap, undefined_cap = int(max_iterations), int(accepted_cap), int(undefined_cap)
     if device is None:
         return [HB.iterate(p, max_iterations, accepted_cap, undefined_cap) for p in problems]
@@ -248,7 +360,49 @@ def background_records(problems, max_iterations=DEFAULT_MAX_ITERATIONS, accepted
     return res
 
 
+def neighbour_means_records(lists, count, device="cuda"):
+    """np.mean of count over every index list of `lists` (an index outside 0 .. len(count) - 1 counts 0, an empty list gives
+    NaN) in one launch of fsq_background_neighbour_means, one wavefront per list: interpolate_signal for many targets at once.
+    device=None: with numpy on the host.  A list longer than 6 560 entries raises ValueError.  Returns float64 [len(lists)]."""
+    lists = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+    count = np.ascontiguousarray(count, dtype=np.float64).reshape(-1)
+    if any(len(l) > NB.JOINT_MAX_NEIGHBOURS for l in lists):
+        raise ValueError("a list is limited to %d entries (FSQ_BACKGROUND_JOINT_MAX_NEIGHBOURS)" % NB.JOINT_MAX_NEIGHBOURS)
+    off = np.zeros(len(lists) + 1, np.int64)
+    np.cumsum([len(l) for l in lists], out=off[1:])
+    flat = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+    if device is None:
+        padded = np.concatenate([count, [0.0]])                                    # (an absent entry reads the 0.0 behind the counts)
+        flat = np.where((flat >= 0) & (flat < len(count)), flat, len(count))
+        with np.errstate(all='ignore'):
+            return np.array([np.mean(padded[flat[a:b]]) if b > a else np.nan for a, b in zip(off[:-1], off[1:])], dtype=np.float64)
+    flat = np.where((flat >= -(1 << 31)) & (flat < 1 << 31), flat, -1).astype(np.int32)    # (the kernel tests the range itself)
+    if not lists:
+        return np.zeros(0, np.float64)
+    torch = _engine._torch()
+    dev = torch.device(device)
+    d_nb, d_off, d_count = (torch.from_numpy(v).to(dev) for v in (flat, off, count))
+    d_out = torch.empty(len(lists), dtype=torch.float64, device=dev)
+    _engine.launch(NB.lib().fsq_background_neighbour_means, "fsq_background_neighbour_means", dev,
+                   d_nb.data_ptr() if len(flat) else None, d_off.data_ptr(), len(lists), d_count.data_ptr() if len(count) else None,
+                   len(count), d_out.data_ptr())
+    return d_out.cpu().numpy()
+
+
 # ---- the reference's call surface ----
+
+def ends_at_zero(z):
+    """is_zero of a reference signal, all(zeros) of a joint one."""
+    return all(z) if isinstance(z, tuple) else z
+
+
+def _one_kind(keys):
+    """Whether the keys are joint signals; mixed kinds raise ValueError."""
+    kinds = set(HS.is_joint(k) for k in keys)
+    if len(kinds) > 1:
+        raise ValueError("joint and one-letter keys are mixed")
+    return bool(kinds) and kinds.pop()
+
 
 def is_multidrop(signal):
     """MCsimlib.is_multidrop (:5589-5597)."""
@@ -280,7 +434,7 @@ def head_truncate(signals, num_cycles=None):
 def counts_to_percent(signals, include_remainders=False, include_multidrop=True, max_cycle=None):
     """MCsimlib.counts_to_percent (:5635-5659): the total is a left-to-right sum in the dict's order."""
     filtered_signals = {(s, z, si): count for (s, z, si), count in signals.items()
-                        if (include_remainders or z) and (include_multidrop or not is_multidrop(s))}
+                        if (include_remainders or ends_at_zero(z)) and (include_multidrop or not is_multidrop(s))}
     filtered_signals = discard_late_signals(signals=filtered_signals, max_cycle=max_cycle)
     total_count = _seq_sum(filtered_signals.values())
     return {k: float(count) / total_count for k, count in filtered_signals.items()}
@@ -317,13 +471,14 @@ def signals_std(experiments, include_remainders=False, include_multidrop=True, m
 
 
 def generate_adjacent_positions(signal, include_multidrop=False):
-    """MCsimlib.generate_adjacent_positions (:5722-5744)."""
+    """MCsimlib.generate_adjacent_positions (:5722-5744).  A joint signal (decrements, zeros, starts) of several letters has
+    the perturbed cycles of its decrements, in their order, whatever their letters; it is a remainder when not all(zeros)."""
     import itertools
-    if len(signal) == 0:
+    if len(signal) == 0 or (HS.is_joint(signal) and len(signal[0]) == 0):
         raise ValueError("Not defined for empty signal.")
-    if not signal[1]:
+    if not ends_at_zero(signal[1]):
         raise ValueError("Not defined for remainders.")
-    if len(set([aa for aa, pos in signal[0]])) != 1:
+    if not HS.is_joint(signal) and len(set([aa for aa, pos in signal[0]])) != 1:
         raise ValueError("Currently only implemented for one label.")
     positions = tuple([pos for aa, pos in signal[0]])
     adjacent_positions = []
@@ -338,14 +493,23 @@ def generate_adjacent_positions(signal, include_multidrop=False):
 
 
 def interpolate_signal(signals, interpolation_target, num_cycles, include_multidrop=False):
-    """MCsimlib.interpolate_signal (:5747-5768): np.mean of the neighbours' values, 0 for an absent one."""
-    amino_acid_set = set([aa for signal in signals for aa, pos in signal[0]])
-    if len(amino_acid_set) != 1:
-        raise ValueError("Currently only implemented for one label.")
-    used_amino_acid = amino_acid_set.pop()
-    adjacent_positions = generate_adjacent_positions(signal=interpolation_target, include_multidrop=include_multidrop)
-    adjacent_signals = [(tuple([(used_amino_acid, pos) for pos in adj]), interpolation_target[1], interpolation_target[2])
-                        for adj in adjacent_positions if all([0 < pos <= num_cycles for pos in adj])]
+    """MCsimlib.interpolate_signal (:5747-5768): np.mean of the neighbours' values, 0 for an absent one.  For joint signals
+    every neighbour keeps the target's letters, zeros and starts and is looked up as it stands: a perturbed tuple that no longer
+    ascends by (cycle, letter) is no experiment's key and counts 0."""
+    if _one_kind(list(signals) + [interpolation_target]):
+        if len(set(len(signal[1]) for signal in list(signals) + [interpolation_target])) != 1:
+            raise ValueError("the keys differ in their label letters")
+        adjacent_positions = generate_adjacent_positions(signal=interpolation_target, include_multidrop=include_multidrop)
+        adjacent_signals = [(tuple([(aa, pos) for (aa, _), pos in zip(interpolation_target[0], adj)]), interpolation_target[1],
+                             interpolation_target[2]) for adj in adjacent_positions if all([0 < pos <= num_cycles for pos in adj])]
+    else:
+        amino_acid_set = set([aa for signal in signals for aa, pos in signal[0]])
+        if len(amino_acid_set) != 1:
+            raise ValueError("Currently only implemented for one label.")
+        used_amino_acid = amino_acid_set.pop()
+        adjacent_positions = generate_adjacent_positions(signal=interpolation_target, include_multidrop=include_multidrop)
+        adjacent_signals = [(tuple([(used_amino_acid, pos) for pos in adj]), interpolation_target[1], interpolation_target[2])
+                            for adj in adjacent_positions if all([0 < pos <= num_cycles for pos in adj])]
     with np.errstate(all='ignore'):
         import warnings
         with warnings.catch_warnings():
@@ -371,16 +535,24 @@ def outlier_z_scores(boc, ac_average, ac_std):
 
 
 def iterative_peak_finding_v3(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold=3, include_multidrop=False,
-                              sigma_subtract=None, device=None, max_iterations=DEFAULT_MAX_ITERATIONS, info=None):
+                              sigma_subtract=None, device=None, max_iterations=DEFAULT_MAX_ITERATIONS, info=None, labels=None):
     """MCsimlib.iterative_peak_finding_v3 (:5932-6040): (peak_list, undefined_peaks, updated_boc_raw, updated_boc_percent).
     peak_list is always [], as in the reference.  device=None: numpy on the host; else the GPU to use.  max_iterations passes
-    without a stop raise RuntimeError.  A dict given as `info` receives stop_reason, n_passes, n_accepted and accepted_keys."""
-    prob = pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop)
+    without a stop raise RuntimeError.  A dict given as `info` receives stop_reason, n_passes, n_accepted and accepted_keys.
+    Joint signals (decrements, zeros, starts) of several label letters take the joint route (joint_pack_problem with the
+    sorted letters `labels`, joint_background_records), which runs on the host: device must be None for them.  Mixed joint
+    and one-letter keys raise ValueError."""
+    joint = _one_kind(list(boc_raw.keys()) + list(boc_percent.keys()) + list(ac_average.keys()) + list(ac_std.keys()))
+    if joint:
+        prob = joint_pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop, labels)
+    else:
+        prob = pack_problem(boc_raw, boc_percent, ac_average, ac_std, num_cycles, sigma_threshold, include_multidrop)
+    records = joint_background_records if joint else background_records
     keys = prob["keys"]
     n_first, n_rest = len(prob["und_first"]), len(prob["und_rest"])
     undefined_cap = n_first + 64 * n_rest
     while True:
-        (res,) = background_records([prob], max_iterations, accepted_cap=4096, undefined_cap=undefined_cap, device=device)
+        (res,) = records([prob], max_iterations, accepted_cap=4096, undefined_cap=undefined_cap, device=device)
         if not res["overflow"] & NB.OVERFLOW_UNDEFINED:
             break
         undefined_cap = n_first + max(res["n_passes"] - 1, 0) * n_rest            # (the passes are the same the second time)

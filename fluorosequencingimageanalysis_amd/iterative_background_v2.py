@@ -3,12 +3,19 @@ command line, with the iteration on the GPU.
 
   python -m fluorosequencingimageanalysis_amd.iterative_background_v2 --boc_file SIGNALS.pkl --ac_file AC.csv --num_cycles N
       [--head_boc 0] [--head_ac 0] [--boc_total T] [--ac_total T] [--ac_use I ...] [--ac_omit I ...] [--omit_multidrop]
-      [--sigma 2] [--output_directory DIR] [--host]
+      [--sigma 2] [--output_directory DIR] [--host] [--labels KC]
 
 Input and output files are pickled signals dictionaries: keys (signal, is_zero, starting_intensity), e.g.
 ((('A', 2), ('A', 5)), True, 2), values counts or a function of counts.  --boc_file and the files the CSV names are SIGNALS.pkl
 dictionaries as lognormal_fitter_v2 writes them.  The CSV has one header row, then one row per ac- dataset: index, file path,
 and columns that are not read (mocks, Edmans, mocks omitted, description).  Remainders (is_zero False) are left out.
+
+A two-colour experiment is given as the JointSignals_HASH.pkl of joint_signals: keys (decrements, zeros, starts) with a tuple
+per label letter, e.g. ((('C', 2), ('K', 5)), (True, True), (1, 1)).  All files must then hold joint signals of the same
+letters (--labels names them when one of them never drops); remainders are the keys with a False among their zeros,
+--omit_multidrop omits the keys in which a cycle repeats, whatever the letters, and the four output files hold joint keys:
+corrected_experiment_HASH.pkl is what sweep_peptide SEQ KC --observed reads.  The iteration on joint signals runs with numpy on the
+host only: --host is required for joint files, and without it the run ends with NotImplementedError before anything is computed.
 
 Datasets of differing cycle numbers are reconciled by two operations, on the boc- dataset, on all ac- datasets, or both:
 --head_* discards the first cycles and renumbers the rest from 1; --*_total then removes every signal with a drop after that
@@ -63,6 +70,9 @@ def make_parser():
                         "simulations are not started simultaneously, e.g. via shell forking, the timestamp hashes should prevent "
                         "file overwrites.")
     p.add_argument('--host', action='store_true', default=False, help="Run the iteration with numpy on the host, not on the GPU.")
+    p.add_argument('--labels', type=str, default=None,
+                   help="The label letters of a two-colour experiment (joint signals), e.g. KC. By default the letters that drop in "
+                        "the files.")
     return p
 
 
@@ -85,6 +95,26 @@ def _dump(obj, path):
     with open(path, 'wb') as f:
         f.write(_py2_pickle_bytes(obj))
     return path
+
+
+def _one_kind_of_files(boc_experiment, ac_experiments):
+    """Whether the files hold joint signals; files of both kinds raise ValueError."""
+    from ._host_signal_sweep import is_joint
+    kinds = set(is_joint(k) for signals in [boc_experiment] + list(ac_experiments.values()) for k in signals)
+    if len(kinds) > 1:
+        raise ValueError("--boc_file and the ac- files must all hold joint signals or all one-letter signals.")
+    return bool(kinds) and kinds.pop()
+
+
+def _joint_labels(labels, boc_experiment, ac_experiments):
+    """The sorted label letters of joint files: --labels, or the letters that drop; every key must have one entry per letter."""
+    keys = [k for signals in [boc_experiment] + list(ac_experiments.values()) for k in signals]
+    found = set(aa for k in keys for aa, c in k[0])
+    letters = tuple(sorted(found if labels is None else set(labels)))
+    if not found <= set(letters) or any(len(k[1]) != len(letters) or len(k[2]) != len(letters) for k in keys):
+        raise ValueError("The files must hold joint signals of the same label letters: %s%s."
+                         % ("".join(letters), "" if labels is not None else " (name them with --labels)"))
+    return letters
 
 
 def main(argv=None, timestamp_epoch=None, device=None):
@@ -110,7 +140,7 @@ def main(argv=None, timestamp_epoch=None, device=None):
             elif len(ac_use_set) > 0 and ac_index not in ac_use_set:
                 continue
             try:
-                ac_signals = {k: count for k, count in _load(ac_filepath).items() if k[1]}
+                ac_signals = {k: count for k, count in _load(ac_filepath).items() if _bg.ends_at_zero(k[1])}
                 ac_experiments.setdefault(ac_index, ac_signals)
             except Exception as e:      # noqa: BLE001 - as the reference: reported and left out
                 print("Could not load " + str(ac_filepath) + " due to " + str(e) + "; omitting.")
@@ -125,7 +155,16 @@ def main(argv=None, timestamp_epoch=None, device=None):
         for ac_index in list(ac_experiments.keys()):
             ac_experiments[ac_index] = _bg.discard_late_signals(signals=ac_experiments[ac_index], max_cycle=args.ac_total)
 
-    boc_experiment = {k: count for k, count in _load(args.boc_file[0]).items() if k[1]}
+    boc_experiment = {k: count for k, count in _load(args.boc_file[0]).items() if _bg.ends_at_zero(k[1])}
+    joint = _one_kind_of_files(boc_experiment, ac_experiments)
+    labels = None
+    if joint:
+        if not args.host:
+            raise NotImplementedError("The files hold joint signals of several label letters: their iteration runs with numpy on "
+                                      "the host only. Give --host.")
+        labels = _joint_labels(args.labels, boc_experiment, ac_experiments)
+    elif args.labels is not None and len(set(args.labels)) > 1:
+        raise ValueError("--labels names several letters, and the files hold one-letter signals.")
     if args.head_boc > 0:
         boc_experiment = _bg.head_truncate(signals=boc_experiment, num_cycles=args.head_boc)
     elif args.head_boc < 0:
@@ -135,7 +174,8 @@ def main(argv=None, timestamp_epoch=None, device=None):
             raise ValueError("--boc_total must be a positive integer.")
         boc_experiment = _bg.discard_late_signals(signals=boc_experiment, max_cycle=args.boc_total)
     if args.omit_multidrop:
-        boc_experiment = {(s, z, si): count for (s, z, si), count in boc_experiment.items() if len(s) == len(set(s))}
+        boc_experiment = {(s, z, si): count for (s, z, si), count in boc_experiment.items()
+                          if (not _bg.is_multidrop(s) if joint else len(s) == len(set(s)))}
 
     experiments = list(ac_experiments.values())
     averaged_ac = _bg.average_signals(experiments=experiments, include_remainders=include_remainders,
@@ -147,7 +187,7 @@ def main(argv=None, timestamp_epoch=None, device=None):
     info = {}
     peak_list, undefined_peaks, updated_boc_raw, updated_boc_percent = _bg.iterative_peak_finding_v3(
         boc_raw=boc_experiment, boc_percent=boc_percent, ac_average=averaged_ac, ac_std=ac_stds, num_cycles=args.num_cycles,
-        sigma_threshold=args.sigma, include_multidrop=include_multidrop, device=_device(args, device), info=info)
+        sigma_threshold=args.sigma, include_multidrop=include_multidrop, device=_device(args, device), info=info, labels=labels)
     # (a key the iteration inserted is not in the experiment: KeyError, as in the reference)
     background_corrected_raw = {k: max(boc_experiment[k] - background_count, 0) for k, background_count in updated_boc_raw.items()}
 
